@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/s of DC-VIC encode+decode at 256x256, q=0, on N x MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,6 +15,10 @@ Weights: deterministic synthetic (dc_vic_amd.synth) -- no checkpoint can be fetc
 
 Output: ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant
 kernel (HIP-event timed inside the timed region) and `cpu_baseline` (the CPU oracle on the host cores).
+
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (float32 / float64, <= 64 MB in all,
+over all ranks; an array too large for its share is cut to a fixed seeded sample of its flattened elements).  The inputs depend only on the arguments, so two
+builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -48,7 +52,44 @@ def parse():
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-kernel-events", action="store_true", help="skip the per-launch HIP events (roofline becomes null)")
     p.add_argument("--event-steps", type=int, default=2, help="eager steps with per-launch HIP events behind the timed region (roofline)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy (float32/float64, <= 64 MB in all)")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be >= 1")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def sample_index(n: int, k: int) -> np.ndarray:
+    """About k sorted distinct indices into range(n), drawn with a fixed seed: the same for the same (n, k) in every run.  Memory is
+    O(k) (draws with replacement, duplicates dropped), not O(n)."""
+    return np.unique(np.random.default_rng(20240601).integers(0, n, size=k, dtype=np.int64))
+
+
+def dump_outputs(out_dir: str, arrays: dict, budget_bytes: int, suffix: str = "") -> dict:
+    """arrays: name -> float32 / float64 numpy array, written as out_dir/<name><suffix>.npy within budget_bytes in all (the
+    .npy headers included).  Arrays that fit in an equal share of what is left are kept whole, smallest first; every larger one
+    is replaced by a fixed seeded sample (sample_index) of its flattened elements that fits its share.  Returns
+    name -> {shape, sampled} for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget_bytes - 4096 * len(arrays)            # .npy headers
+    assert left > 0, "dump budget too small for the headers"
+    info = {}
+    order = sorted(arrays, key=lambda n_: arrays[n_].nbytes)
+    for i, name in enumerate(order):
+        v = arrays[name]
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        shape, sampled = list(v.shape), False
+        share = left // (len(order) - i)
+        if v.nbytes > share:
+            v, sampled = v.reshape(-1)[sample_index(v.size, share // v.itemsize)], True
+        left -= v.nbytes
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(v))
+        info[name] = {"shape": shape, "sampled": sampled}
+    return {n_: info[n_] for n_ in arrays}
 
 
 def cpu_baseline(sd, quality: int):
@@ -141,7 +182,7 @@ def main():
         tg = time.perf_counter()
         table = gather_rate_table(table, dist, dev)       # the only collective: a few KB over RCCL
         gather_s[0] += time.perf_counter() - tg
-        return imgs, table
+        return imgs, table, r
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -168,12 +209,31 @@ def main():
     gather_s[0] = 0.0
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        imgs, table = step()
+        imgs, table, last = step()
     torch.cuda.synchronize(dev)
     dt_local = time.perf_counter() - t0       # this rank's own time (before the barrier): shows load imbalance
     sync()
     dt = time.perf_counter() - t0
     log(f"{a.steps} timed step(s) in {dt:.2f}s")
+    dumped = None
+    if a.dump_outputs:
+        # copied to the host now, before any further step can reuse the buffers; what compress_batch + decompress_batch return.
+        # Every rank writes its own shard (suffix _rank<r> when world > 1) within an equal part of the 64 MB; the gathered rate
+        # table is the same on every rank and is written by rank 0 only.
+        streams = last["string_lists"]
+        arrays = {
+            "images": imgs.float().cpu().numpy(),
+            "vq_indices": last["vq_indices"].cpu().numpy().astype(np.float64),
+            "y_hat": last["y_hat"].float().cpu().numpy(),
+            "z_hat": last["z_hat"].float().cpu().numpy(),
+            "stream_lengths": np.array([[len(s) for s in sl] for sl in streams], dtype=np.float64),
+            "stream_bytes": np.frombuffer(b"".join(b"".join(sl) for sl in streams), dtype=np.uint8).astype(np.float32),
+            "pred_bits": np.stack([last["pred_y_bit"], last["pred_z_bit"]], axis=1).astype(np.float64),
+        }
+        if rank == 0:
+            arrays["rate_table"] = np.asarray(table, dtype=np.float64)
+        dumped = dump_outputs(a.dump_outputs, arrays, DUMP_LIMIT_BYTES // world, suffix=f"_rank{rank}" if world > 1 else "")
+        log(f"outputs of the last timed step written to {a.dump_outputs}")
     # Per-launch HIP events for the roofline.  The timed steps replay the two network segments as hipGraphs, which cannot carry
     # per-launch events, so the SAME step is run `--event-steps` more times right behind the timed region with the events on (eager
     # launches of the same kernels with the same arguments, on the stream they run on); rocprofv3 of this command reports the same
@@ -241,6 +301,7 @@ def main():
             "per_rank_host_cores": [int(p_[2]) for p_ in per_rank],
             "stage_ms_per_step": stage_ms,
             "avg_pred_bpp": float(table[:, 1].mean() / (IH * IW)),
+            "dumped_outputs": dumped,
             # ALGORITHMIC work rate (1 009.6 GF per 256^2 image at direct-convolution cost) per GPU: a throughput in
             # TFLOP/s of useful work, NOT a utilisation (Winograd skips multiplies); the utilisation is
             # end_to_end_executed_conv_mfma_frac_of_f32_peak below

@@ -33,6 +33,7 @@ from .elic import ElicDualBetaFtFeatFusionDecoder, ElicDualBetaFtVqScEncoder  # 
 from .entropy import EntropyBottleneck, GaussianMeanScaleConditional, get_scale_table, host_threads
 from .fusion import build_vq_fusion_module
 from .hyperprior import Minnen20HyperDecoder, Minnen20HyperEncoder  # noqa: F401
+from .layers import allow_bf16
 from .registry import (CONTEXTMODEL_REGISTRY, DECODER_REGISTRY, ENCODER_REGISTRY, ENTROPYMODEL_REGISTRY,
                        HYPERDECODER_REGISTRY, HYPERENCODER_REGISTRY, LRP_REGISTRY, MODEL_REGISTRY, VQ_ESTIMATOR_REGISTRY)
 from .swin import DualBlockSwinVqEstimator  # noqa: F401
@@ -42,6 +43,28 @@ Tensor = torch.Tensor
 
 SPLIT_DECODE_RESOLUTION = 1024   # hyperprior_vic_model.py:25-27
 SPLIT_WINDOW_SIZE = 512
+# Marked layers that stay fp32 in decoder precision "bf16" (the fidelity rule of the mode: >= 50 dB PSNR against the fp32 reconstruction,
+# with margin for the uint8 PNG).  bf16 rounding errors compound through the decoder: every layer alone costs less than the bar, all of them
+# together 44.9 dB.  These are the 16 largest contributors, measured one layer at a time (tools/bf16_layer_sensitivity.py,
+# profiles/bf16_layer_sensitivity.json): the three Upsample convs, the SFT scale convs, the mid blocks and the first full-resolution block.
+BF16_KEEP_FP32 = (
+    "vq_model.decoder.up.3.upsample.conv",
+    "vq_model.decoder.mid.block_1.conv2",
+    "fusion_module.fusion_modules.block_1_4.scale.2",
+    "vq_model.decoder.up.2.upsample.conv",
+    "vq_model.decoder.mid.block_1.conv1",
+    "vq_model.decoder.up.1.upsample.conv",
+    "fusion_module.fusion_modules.block_1_4.scale.0",
+    "fusion_module.fusion_modules.block_1_2.scale.2",
+    "fusion_module.fusion_modules.block_1_8.scale.0",
+    "fusion_module.fusion_modules.block_1_2.scale.0",
+    "fusion_module.fusion_modules.block_1_8.scale.2",
+    "vq_model.decoder.mid.block_2.conv2",
+    "vq_model.decoder.mid.block_2.conv1",
+    "vq_model.decoder.up.3.block.0.conv1",
+    "vq_model.decoder.up.3.block.0.conv2",
+    "vq_model.decoder.up.3.block.1.conv1",
+)
 SPLIT_STRIDE = 256
 # tiling windows of a > 1024-px image decoded / encoded per kernel launch (the reference loops one by one): 32 x 512^2 windows
 # are ~25 GB of activations at the VQGAN decoder's widest point -- nothing on a 288 GB part
@@ -297,7 +320,31 @@ class HyperpriorVicModel(BaseModel):
         self.enc_vq_input = enc_vq_input
         self.n_embed = self.vq_model.n_embed
         self.model_stride, self.y_stride = 64, 16
+        self._decoder_precision = "fp32"
         self.to(self.device)
+
+    DECODER_PRECISIONS = ("fp32", "bf16")
+
+    @property
+    def decoder_precision(self) -> str:
+        """"fp32" (default) or "bf16": the arithmetic of the VQGAN decoder's and the SFT fusion blocks' 3x3 convolutions."""
+        return self._decoder_precision
+
+    def set_decoder_precision(self, precision: str) -> None:
+        """"bf16" runs the 3x3 convolutions of the frozen VQGAN decoder and of the SFT fusion blocks (the layers after the estimator's
+        argmax, layers.allow_bf16) on the bf16-MFMA kernel; "fp32" restores the default kernels bit for bit.  Bitstreams, VQ indices,
+        symbols, latents and the estimator's logits do not depend on it, only the reconstruction does (>= 50 dB PSNR against fp32).
+        Honoured by run_model, decompress_batch / decompress and decode_split; hipGraph segments are keyed by it."""
+        if precision not in self.DECODER_PRECISIONS:
+            raise ValueError(f"decoder precision must be one of {self.DECODER_PRECISIONS}, got {precision!r}")
+        on = precision == "bf16"
+        allow_bf16(self.vq_model.decoder, on)
+        allow_bf16(self.fusion_module, on)
+        mods = dict(self.named_modules())
+        for name in BF16_KEEP_FP32:
+            if name in mods:
+                mods[name].bf16_keep_fp32 = on
+        self._decoder_precision = precision
 
     def _build_subnets(self) -> None:
         sub = self.opt["subnet"]
@@ -623,7 +670,7 @@ class HyperpriorDualCondVicModel(HyperpriorVicModel):
         if max(H, W) > SPLIT_DECODE_RESOLUTION:
             fake = self.decode_split(y_hat, w, beta_rate=beta_rate, beta_vq=beta_vq)
         elif self._graphs.usable(len(string_lists) * padH * padW):
-            fake = self._graphs.run(("dec", tuple(y_hat.shape), q, float(beta_rate), float(beta_vq)),
+            fake = self._graphs.run(("dec", tuple(y_hat.shape), q, float(beta_rate), float(beta_vq), self.decoder_precision),
                                     lambda yh: self._decode(yh, w, beta_rate, beta_vq)[0], [y_hat.contiguous()],
                                     keep=lambda: list(self.decoder._vec_cache.values()))
         else:

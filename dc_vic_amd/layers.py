@@ -27,13 +27,15 @@ class _Packed(nn.Module):
     def _key(self):
         return tuple((p.data_ptr(), p._version, str(p.device)) for p in self.parameters(recurse=False))
 
-    def _get_plan(self):
+    def _get_plan(self, bf16: bool = True):
+        """`bf16=False`: the plan runs fp32 whatever allow_bf16 set (training: train/autograd.conv)."""
         k = self._key()
         if self._plan is None or self._plan_key != k:
             self._plan = self._build_plan()
             self._plan_key = k
         self._plan.wino = bool(getattr(self, "wino", False))
         self._plan.wino44 = bool(getattr(self, "wino44", False))
+        self._plan.bf16 = bf16 and bool(getattr(self, "bf16", False)) and not getattr(self, "bf16_keep_fp32", False)
         return self._plan
 
     def _build_plan(self):
@@ -55,6 +57,8 @@ class Conv2d(_Packed):
         self.asym_pad, self.upsample = asym_pad, upsample
         self.wino = False     # allow_winograd(): set only where no integer decision depends on this layer's exact bits
         self.wino44 = False   # allow_winograd(f44=True): F(4x4, 3x3) too -- only AFTER the path's last integer decision
+        self.bf16 = False     # allow_bf16(): the bf16-MFMA kernel (decoder precision "bf16"), same layers as wino44
+        self.bf16_keep_fp32 = False   # set by the owner: a marked layer whose bf16 rounding costs too much fidelity stays fp32
         self.weight = nn.Parameter(torch.empty(out_ch, in_ch, kernel_size, kernel_size), requires_grad=False)
         self.bias = nn.Parameter(torch.empty(out_ch), requires_grad=False) if bias else None
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
@@ -105,6 +109,18 @@ def allow_winograd(module: nn.Module, on: bool = True, f44: bool = False) -> nn.
         if isinstance(m, Conv2d) and m.kernel_size == 3 and m.stride == 1 and m.padding == 1 and not m.asym_pad:   # (incl. the Upsample convs)
             m.wino = on
             m.wino44 = bool(on and f44)
+    return module
+
+
+def allow_bf16(module: nn.Module, on: bool = True) -> nn.Module:
+    """Let every Conv2d(k3, s1, p1) under `module`, the Upsample convs included, run on the bf16-MFMA kernel (csrc/conv_bf16.hip: bf16
+    operands, fp32 accumulation) when the launch is eligible -- the layers allow_winograd(f44=True) marks.  Called ONLY through
+    set_decoder_precision for the frozen VQGAN decoder and the SFT fusion blocks, after the estimator's argmax: bitstreams, indices,
+    symbols and logits cannot move, only the reconstruction (contract: >= 50 dB PSNR against the fp32 reconstruction).  Never for the
+    encoder, the hyperprior, CHARM, the ELIC decoder or the estimator.  A launch the kernel does not take stays on the fp32 kernels."""
+    for m in module.modules():
+        if isinstance(m, Conv2d) and m.kernel_size == 3 and m.stride == 1 and m.padding == 1 and not m.asym_pad:
+            m.bf16 = bool(on)
     return module
 
 

@@ -70,6 +70,8 @@ def conv_kernel_name(variant: int) -> str:
         return "conv3x3_wino_ups_kernel(ConvKArgs)"
     if variant == 9104:
         return "conv3x3_wino44_kernel(ConvKArgs)"
+    if variant in (9300, 9301):
+        return f"void conv3x3_bf16_kernel<{'true' if variant == 9301 else 'false'}>(Bf16Args, ConvKArgs)"
     if 9200 <= variant < 9210:
         return f"void thin_cout_kernel<{variant - 9200}>(ThinArgs)"
     if 9210 <= variant < 9220:
@@ -145,6 +147,7 @@ THIN_ENABLED = os.environ.get("DCVIC_THIN", "1") != "0"       # VALU kernels for
 WINO44_MIN_BLOCKS = int(os.environ.get("DCVIC_WINO44_MIN_BLOCKS", "16"))   # workgroup tiles PER IMAGE below which F(2x2) / direct run
 WINO44_ENABLED = os.environ.get("DCVIC_WINO44", "1") != "0"   # F(4x4,3x3) for the layers that opted in (ConvPlan.wino44)
 WINO_MIN_BLOCKS = int(os.environ.get("DCVIC_WINO_MIN_BLOCKS", "16"))   # workgroups PER IMAGE below which the direct kernels run
+BF16_KERNEL_VARIANT = 9300        # conv3x3_bf16_kernel<false>; 9301 with the fused x2 upsample
 
 
 class ConvPlan:
@@ -160,6 +163,11 @@ class ConvPlan:
     _wino44_pack = None
     last_gn_part = None   # (partial statistics [N, Cout, n_pt, 2], n_pt) written by the last call when gn_stats was asked AND the F(4x4) kernel ran
     _wino_ups_pack = None
+    bf16 = False          # set by the owner: bf16-MFMA kernel (csrc/conv_bf16.hip) when eligible -- decoder precision "bf16" only
+    _bf16_pack = None
+    last_bf16 = False     # whether the last call ran on the bf16 kernel
+    bf16_launches = 0     # calls that ran on the bf16 kernel / on the fp32 kernels (coverage record)
+    fp32_launches = 0
 
     def __init__(self, weight: Tensor, bias: Optional[Tensor], kind: str = "conv", stride: int = 1,
                  pad: Tuple[int, int] = (0, 0), upsample: bool = False):
@@ -271,6 +279,17 @@ class ConvPlan:
             return False
         return ty * tx * ((self.Cout + 63) // 64) >= WINO_MIN_BLOCKS
 
+    def _bf16_ok(self, srcs, out_hw) -> bool:
+        """bf16-kernel eligibility: Conv2d(k3, s1, p1), optionally behind the nearest x2 upsample, every source a multiple of 8 channels,
+        at least 16 output channels.  A function of the LAYER only -- never of N or of the image size."""
+        if self.kind != "conv" or self.stride != 1 or self.pad != (1, 1) or (self.KH, self.KW) != (3, 3) or self._w is None:
+            return False
+        if out_hw is not None:
+            H, W = srcs[0].shape[2:]
+            if tuple(out_hw) != ((2 * H, 2 * W) if self.upsample else (H, W)):
+                return False
+        return self.Cout >= 16 and all(s.shape[1] % 8 == 0 for s in srcs)
+
     @staticmethod
     def _pack(d: ConvDesc, w: Tensor) -> Tensor:
         nbytes = lib().dcvic_conv_packed_bytes(C.byref(d))
@@ -291,6 +310,7 @@ class ConvPlan:
         """`gn_stats`: the caller's next op is a GroupNorm over exactly this output; when the launch runs on the F(4x4) kernel its epilogue
         also writes the GroupNorm partial sums (self.last_gn_part, else None) and the GroupNorm skips its statistics pass."""
         self.last_gn_part = None
+        self.last_bf16 = False
         if isinstance(srcs, Tensor):
             srcs = [srcs]
         N, _, H, W = _chk4(srcs[0], "conv src0")
@@ -341,6 +361,27 @@ class ConvPlan:
             if sc.shape[0] not in (1, N):
                 raise ValueError("conv affine batch must be 1 or N")
         st = _stream()
+        if self.bf16 and init is None and self._bf16_ok(srcs, out_hw):
+            if self._bf16_pack is None:       # owned by the plan: a weight change builds a new plan (layers._Packed key) and re-packs
+                nbytes = lib().dcvic_conv3x3_bf16_packed_bytes(self.Cin, self.Cout)
+                self._bf16_pack = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=self._w.device)
+                check(lib().dcvic_conv3x3_bf16_pack_f32(_p(self._w), _p(self._bf16_pack), self.Cin, self.Cout, st), "conv3x3_bf16_pack")
+            io.Hout, io.Wout = Hf, Wf
+            io.osy = io.osx = 1
+            io.ooy = io.oox = 0
+            ups = 1 if self.upsample else 0
+            self.last_bf16 = True
+            self.bf16_launches += 1
+            if _EVENTS is not None:
+                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+                check(lib().dcvic_conv3x3_bf16_f32(self.Cin, self.Cout, ups, _p(self._bf16_pack), C.byref(io), st), "conv3x3_bf16")
+                e1.record()
+                _EVENTS.append((BF16_KERNEL_VARIANT + ups, 2.0 * N * Hf * Wf * self.Cout * self.Cin * 9, e0, e1, (self.Cin, self.Cout, 9, 1, ups, H, W, N)))
+            else:
+                check(lib().dcvic_conv3x3_bf16_f32(self.Cin, self.Cout, ups, _p(self._bf16_pack), C.byref(io), st), "conv3x3_bf16")
+            return out
+        self.fp32_launches += 1
         if THIN_ENABLED and self.kind == "conv" and not self.upsample and not self.ups_phases and self.stride == 1 and self.pad == (1, 1) \
                 and (self.KH, self.KW) == (3, 3) and self._w is not None and len(srcs) == 1 and init is None and affine is None \
                 and (out_hw is None or tuple(out_hw) == (H, W)) and H * W >= THIN_MIN_PIXELS \

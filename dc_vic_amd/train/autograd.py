@@ -191,7 +191,8 @@ def conv(ctx: Ctx, x: Var, mod, act: int = ops.ACT_NONE) -> Var:
                 plan.wino = bool(getattr(mod, "wino", False))    # (the SFT fusion blocks train; their 3x3 convs stay on Winograd)
                 plan.wino44 = plan.wino and bool(getattr(mod, "wino44", False))
         else:
-            plan = mod._get_plan()
+            plan = mod._get_plan(bf16=False)
+    # training ignores the decoder precision: the plans above copy wino / wino44 and never bf16 (layers.allow_bf16 is inference only)
     y = plan(xin, act=act)
     out = Var(y)
 

@@ -174,6 +174,23 @@ int dcvic_conv3x3_wino44_f32(int Cin, int Cout, const float* packed, const dcvic
  * dcvic_groupnorm_part_f32.  Fixed summation order, no atomics. */
 int dcvic_wino44_stats_tiles(int H, int W);
 int dcvic_conv3x3_wino44_stats_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream);
+/* Opt-in bf16 reconstruction (csrc/conv_bf16.hip): Conv2d(k3, s1, p1), with `upsample` behind a nearest x2 (ldm Upsample,
+ * model.py:42-57), as an implicit GEMM on bf16 MFMA with fp32 accumulation.  Replaces, when the model is set to decoder precision bf16,
+ * the same operators as dcvic_conv3x3_wino44_f32 / dcvic_conv3x3_wino_ups_f32 -- the frozen VQGAN decoder and the SFT fusion blocks:
+ * ldm/modules/diffusionmodules/model.py:42-57, 82-141, 462-568; codeformer_layers.py:20-67; vq_fusion_module.py:78-126 -- and never
+ * anything upstream of an integer decision.  Weights w[Cout][Cin][3][3] are rounded to bf16 once (round to nearest even) and packed
+ * in MFMA operand order, zero-padded to 128 output x 32 input channels: dcvic_conv3x3_bf16_packed_bytes = ceil(Cout/128)*128 *
+ * ceil(Cin/32)*32 * 9 * 2 bytes.  Activations stay fp32 in memory and are rounded to bf16 while staged (NaN stays NaN).
+ * io: N x H x W input (low resolution when `upsample`), Hout = Hfull = H (2H), Wout = Wfull = W (2W), any H, W, N; every source a
+ * multiple of 8 channels (fused channel concatenation); epilogue bias -> act -> (+res) -> (affine) of dcvic_conv2d_f32; no init.
+ * Reduction order per output element: 32-channel chunks, taps, MFMA k order -- a function of the layer only (no split-K, no atomics):
+ * deterministic and batch-invariant.  No GroupNorm statistics (the GroupNorm that follows makes its own pass).
+ * dcvic_conv3x3_bf16_mfma_shape: 32 (v_mfma_f32_32x32x16_bf16) or 16 (v_mfma_f32_16x16x32_bf16), the shape of this build's kernel
+ * and pack order. */
+size_t dcvic_conv3x3_bf16_packed_bytes(int Cin, int Cout);
+int dcvic_conv3x3_bf16_mfma_shape(void);
+int dcvic_conv3x3_bf16_pack_f32(const float* w, void* packed, int Cin, int Cout, void* stream);
+int dcvic_conv3x3_bf16_f32(int Cin, int Cout, int upsample, const void* packed, const dcvic_conv_io* io, void* stream);
 /* Conv2d(k3, s1, p1) with Cout <= 4 (Cin % 8 == 0) or Cin <= 4 (csrc/thin.hip): the VQGAN decoder's conv_out (128 -> 3,
  * ldm/modules/diffusionmodules/model.py:553-557) and the VQGAN encoder's conv_in (3 -> 128, model.py:388-392).  HBM-bound fp32
  * fmaf chains on the vector ALU in exactly the reduction order of dcvic_conv2d_f32, hence BIT-IDENTICAL to it; unpacked weights

@@ -16,6 +16,8 @@ MI355X additions (not in the reference, which is single-GPU, README.md:64-65):
     json a single-GPU run writes.
   * --synthetic_weights skips --model_path and loads the deterministic synthetic weights (no checkpoint
     can be fetched offline); the YAML's vq_model.ckpt_path is ignored when it does not exist.
+  * --decoder_precision bf16 runs the VQGAN decoder's and the SFT fusion blocks' 3x3 convolutions on bf16 MFMA (model.set_decoder_precision):
+    the .bin files, _bitrates.csv and _avg_bitrate.json are those of the default fp32 run; only the PNGs differ (>= 50 dB PSNR).
 """
 from __future__ import annotations
 
@@ -51,14 +53,21 @@ def write_png(path: str, u8_hwc: np.ndarray) -> None:
     Image.fromarray(u8_hwc, mode="RGB").save(path)
 
 
-def main():
+def build_parser():
     p = compress_arg_parser()
     p.add_argument("--batch_size", type=int, default=1)
     p.add_argument("--synthetic_weights", action="store_true")
     p.add_argument("--io_workers", type=int, default=0, help="PNG decode / encode threads (0: min(8, this rank's share of the cores))")
     p.add_argument("--gpus", type=int, default=0, help="shard the folder over N GPUs of this node: without a launcher this process starts "
                                                         "the N ranks itself (0: as launched -- WORLD_SIZE ranks under torch.distributed.run, else 1)")
-    args = p.parse_args()
+    p.add_argument("--decoder_precision", choices=("fp32", "bf16"), default="fp32",
+                   help="arithmetic of the VQGAN decoder / SFT fusion 3x3 convolutions: bf16 changes only the PNGs (>= 50 dB against fp32), "
+                        "never the .bin files or the csv / json")
+    return p
+
+
+def main():
+    args = build_parser().parse_args()
     if args.gpus > 1 and not launched_by_a_launcher():
         sys.exit(self_launch(args.gpus, need_gpus=args.device.startswith("cuda")))      # parent: never touches the GPU
     if args.gpus > 0 and int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -81,7 +90,7 @@ def main():
             dist_.init_process_group("gloo", rank=rank, world_size=world)
         dist = dist_
 
-    overrides = {k: v for k, v in vars(args).items() if k not in ("batch_size", "synthetic_weights", "io_workers", "gpus")}
+    overrides = {k: v for k, v in vars(args).items() if k not in ("batch_size", "synthetic_weights", "io_workers", "gpus", "decoder_precision")}
     overrides["device"] = device
     if device == "cuda":
         device = overrides["device"] = f"cuda:{torch.cuda.current_device()}"      # the reference's `-d cuda`
@@ -103,6 +112,7 @@ def main():
     else:
         model.load_learned_weight(ckpt_path=args.model_path)
     model.codec_setup()
+    model.set_decoder_precision(args.decoder_precision)
 
     # shard by padded pixel count (images are independent units)
     sizes = []

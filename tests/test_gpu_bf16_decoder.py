@@ -80,7 +80,9 @@ def _ref(srcs, w, b, ups, act, res, aff):
     return y, mag
 
 
-def _run(Cin_list, Cout, N, H, W, ups=False, bias=True, act=None, res=False, aff=False, seed=0):
+def _run(Cin_list, Cout, N, H, W, ups=False, bias=True, act=None, res=False, aff=False, seed=0, views=False):
+    """views: the sources are channel slices of one buffer, with NaN channels around each (a read outside a source poisons the
+    result), and the output is a channel slice of a larger buffer whose other channels must keep their sentinel."""
     from dc_vic_amd import ops
     g = torch.Generator().manual_seed(seed)
     Cin = sum(Cin_list)
@@ -90,10 +92,25 @@ def _run(Cin_list, Cout, N, H, W, ups=False, bias=True, act=None, res=False, aff
     Ho, Wo = (2 * H, 2 * W) if ups else (H, W)
     r = torch.randn((N, Cout, Ho, Wo), generator=g).to(DEV) if res else None
     a = (torch.randn((N, Cout), generator=g).mul(0.3).to(DEV), torch.randn((N, Cout), generator=g).mul(0.3).to(DEV)) if aff else None
+    out = None
+    if views:
+        gap = 8
+        buf = torch.full((N, Cin + gap * (len(Cin_list) + 1), H, W), float("nan"), device=DEV)
+        o = gap
+        for k, s in enumerate(srcs):
+            buf[:, o:o + s.shape[1]] = s
+            srcs[k] = buf[:, o:o + s.shape[1]]
+            o += s.shape[1] + gap
+        out_buf = torch.full((N, Cout + 24, Ho, Wo), -12345.0, device=DEV)
+        out = out_buf[:, 16:16 + Cout]
     plan = ops.ConvPlan(w.to(DEV), b.to(DEV) if b is not None else None, "conv", pad=(1, 1), upsample=ups)
     plan.bf16 = True
-    y = plan(srcs if len(srcs) > 1 else srcs[0], act=ops.ACT_LRELU02 if act == "lrelu" else ops.ACT_NONE, res=r, affine=a)
+    y = plan(srcs if len(srcs) > 1 else srcs[0], out=out, act=ops.ACT_LRELU02 if act == "lrelu" else ops.ACT_NONE, res=r, affine=a)
     torch.cuda.synchronize()
+    if views:
+        assert y.data_ptr() == out.data_ptr()
+        assert bool((out_buf[:, :16] == -12345.0).all()) and bool((out_buf[:, 16 + Cout:] == -12345.0).all()), \
+            "the output was written outside its channel slice"
     assert plan.last_bf16 and plan.bf16_launches == 1, "the launch did not run on the bf16 kernel"
     ref, mag = _ref(srcs, w, b, ups, act, r, a)
     err = (y.cpu().double() - ref).abs()
@@ -132,6 +149,16 @@ def test_kernel_ragged_and_batch_sizes():
     _run([64], 96, 3, 72, 136, res=True, seed=22)
     _run([40], 48, 3, 5, 7, ups=True, seed=23)
     _run([128], 128, 1, 1, 1, seed=24)
+
+
+def test_kernel_three_sources_through_views():
+    """The fusion buffers' layout: up to three sources read as channel slices of one buffer (each with its own offset and the buffer's
+    batch stride), the output written into a channel slice, N = 3; with and without the fused upsample."""
+    _run([192, 64, 256], 128, 3, 12, 20, seed=31, views=True)
+    _run([192, 64, 256], 64, 3, 6, 10, ups=True, seed=32, views=True)
+    _run([192, 64, 256], 96, 1, 7, 9, act="lrelu", res=True, aff=True, seed=33, views=True)
+    _run([16, 48], 64, 3, 9, 13, ups=True, act="lrelu", res=True, aff=True, seed=34, views=True)
+    _run([64], 96, 3, 17, 29, res=True, seed=35, views=True)
 
 
 def test_kernel_batch_invariant():

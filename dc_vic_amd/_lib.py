@@ -73,6 +73,8 @@ SYMBOLS = [
     "dcvic_groupnorm_bwd_f32", "dcvic_layernorm_c_bwd_blocks", "dcvic_layernorm_c_bwd_f32", "dcvic_softmax_c_bwd_f32",
     "dcvic_swin_attn_bwd_f32", "dcvic_reduce_loss_f32", "dcvic_cross_entropy_f32", "dcvic_adam_step_f32", "dcvic_clip_scale_f32",
     "dcvic_resample2_f32", "dcvic_s2d_f32", "dcvic_maxpool3s2_f32", "dcvic_lpips_tap_f32",
+    # full-reference metrics (csrc/metrics.hip)
+    "dcvic_l2pool_f32", "dcvic_pair_moments_workspace_doubles", "dcvic_pair_moments_f64", "dcvic_dists_score_f64", "dcvic_lpips_score_f64",
 ]
 
 _lib = None
@@ -99,6 +101,8 @@ def lib() -> C.CDLL:
     L.dcvic_wino44_packed_bytes.restype = C.c_size_t
     L.dcvic_conv3x3_bf16_packed_bytes.restype = C.c_size_t
     L.dcvic_conv_wgrad_workspace_floats.restype = C.c_longlong
+    L.dcvic_pair_moments_workspace_doubles.restype = C.c_longlong
+    L.dcvic_pair_moments_workspace_doubles.argtypes = [C.c_longlong, C.c_longlong]
     L.dcvic_tables_create_host.restype = C.c_void_p
     L.dcvic_rans_decoder_create_host.restype = C.c_void_p
     L.dcvic_tables_destroy_host.argtypes = [C.c_void_p]

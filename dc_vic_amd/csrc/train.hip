@@ -816,9 +816,9 @@ __global__ __launch_bounds__(256) void s2d_kernel(const float* __restrict__ in, 
         out[i] = (y < Ho && x < Wo) ? in[((p * r * r + d) * Ho + y) * Wo + x] : 0.f;
     }
 }
-extern "C" int dcvic_s2d_f32(const float* in, float* out, long long planes, int H, int W, int r, int pad, int inverse, void* stream) {
-    DCVIC_CHECK_ARG(in && out && planes > 0 && r >= 1, "s2d: bad argument");
-    const int Ho = (H + 2 * pad) / r, Wo = (W + 2 * pad) / r;
+extern "C" int dcvic_s2d_f32(const float* in, float* out, long long planes, int H, int W, int r, int pad, int Ho, int Wo, int inverse,
+                             void* stream) {
+    DCVIC_CHECK_ARG(in && out && planes > 0 && r >= 1 && Ho >= 1 && Wo >= 1, "s2d: bad argument");
     const long long total = inverse ? planes * H * W : planes * r * r * Ho * Wo;
     s2d_kernel<<<dcvic_cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(in, out, planes, H, W, r, pad, Ho, Wo, inverse);
     DCVIC_CHECK_LAUNCH("s2d");

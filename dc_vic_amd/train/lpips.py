@@ -78,19 +78,21 @@ class LPIPSAlex(nn.Module):
         return self._stem[0]
 
 
-def s2d(ctx: Ctx, x: Var, r: int, pad: int) -> Var:
+def s2d(ctx: Ctx, x: Var, r: int, pad: int, k: int) -> Var:
+    """Space-to-depth(r) of x zero-padded by `pad`, with as many r x r blocks as a k-tap / stride-r / pad-`pad` conv reads: its
+    output o covers blocks o .. o + (k-1)//r, and the last o is (H + 2 pad - k) // r (blocks past the image are zero)."""
     xd = A._dense(x.data)
     N, Cc, H, W = _chk4(xd, "s2d x")
-    Ho, Wo = (H + 2 * pad) // r, (W + 2 * pad) // r
+    Ho, Wo = (H + 2 * pad - k) // r + 1 + (k - 1) // r, (W + 2 * pad - k) // r + 1 + (k - 1) // r
     y = torch.empty((N, Cc * r * r, Ho, Wo), dtype=torch.float32, device=xd.device)
-    check(lib().dcvic_s2d_f32(_p(xd), _p(y), C.c_longlong(N * Cc), H, W, r, pad, 0, _stream()), "s2d")
+    check(lib().dcvic_s2d_f32(_p(xd), _p(y), C.c_longlong(N * Cc), H, W, r, pad, Ho, Wo, 0, _stream()), "s2d")
     out = Var(y)
 
     def back():
         if out.grad is None or not x.needs_grad:
             return
         dx = torch.empty_like(xd)
-        check(lib().dcvic_s2d_f32(_p(A._dense(out.grad)), _p(dx), C.c_longlong(N * Cc), H, W, r, pad, 1, _stream()), "s2d_bwd")
+        check(lib().dcvic_s2d_f32(_p(A._dense(out.grad)), _p(dx), C.c_longlong(N * Cc), H, W, r, pad, Ho, Wo, 1, _stream()), "s2d_bwd")
         A.acc(x, dx)
     ctx.tape.append(back)
     return out
@@ -121,7 +123,7 @@ def features(ctx: Ctx, L: LPIPSAlex, img: Var) -> List[Var]:
     s = A.const((1.0 / sc - 1.0).contiguous())                    # x * (1 + s) + t = (x - shift) / scale
     t = A.const((-sh / sc).contiguous())
     x = A.chan_affine(ctx, img, s, t)
-    f1 = A.conv(ctx, s2d(ctx, x, 4, 2), L.stem(), act=ops.ACT_RELU)
+    f1 = A.conv(ctx, s2d(ctx, x, 4, 2, 11), L.stem(), act=ops.ACT_RELU)
     f2 = A.conv(ctx, maxpool3s2(ctx, f1), L.net.slice2[0], act=ops.ACT_RELU)
     f3 = A.conv(ctx, maxpool3s2(ctx, f2), L.net.slice3[0], act=ops.ACT_RELU)
     f4 = A.conv(ctx, f3, L.net.slice4[0], act=ops.ACT_RELU)

@@ -381,10 +381,33 @@ int dcvic_resample2_f32(int down, const float* in, float* out, long long planes,
 
 /* LPIPS(alex) pieces (src/losses/perceptual_loss.py:10-30; parity unpinned -- the lpips package is not in the reference tree):
  * zero-padded space-to-depth and its adjoint (the 11x11/s4/p2 stem as a 3x3 conv over 48 channels), MaxPool2d(3, 2) forward
- * (dx == NULL) / backward, and one tap: per-pixel sum_c w[c] (f0/|f0| - f1/|f1|)^2 plus the gradient w.r.t. f1. */
-int dcvic_s2d_f32(const float* in, float* out, long long planes, int H, int W, int r, int pad, int inverse, void* stream);
+ * (dx == NULL) / backward, and one tap: per-pixel sum_c w[c] (f0/|f0| - f1/|f1|)^2 plus the gradient w.r.t. f1.
+ * s2d: the depth tensor is [planes][r*r][Ho][Wo] blocks of the image zero-padded by `pad` at the top / left; blocks reaching past the
+ * image read as zero, so Ho / Wo may exceed (H + 2 pad) / r -- a K-tap stride-r conv needs (H + 2 pad - K) / r + 1 + (K - 1) / r. */
+int dcvic_s2d_f32(const float* in, float* out, long long planes, int H, int W, int r, int pad, int Ho, int Wo, int inverse, void* stream);
 int dcvic_maxpool3s2_f32(const float* x, float* y, unsigned char* argmax, const float* dy, float* dx, long long planes, int H, int W, void* stream);
 int dcvic_lpips_tap_f32(const float* f0, const float* f1, const float* w, float* pix, float* df1, int N, int C, int HW, float gscale, void* stream);
+
+/* Full-reference metrics (scripts/calc_metrics.py:174-215 computes LPIPS and DISTS per image; csrc/metrics.hip).  DISTS restates the
+ * DISTS_pytorch package (Ding et al. 2020; parity unpinned -- the package is not in the reference tree):
+ *   l2pool:       y = sqrt(depthwise_conv2d(x^2, g, stride 2, pad 1) + 1e-12), g = [[1,2,1],[2,4,2],[1,2,1]] / 16 (L2pooling), zero
+ *                 padding, output floor((H-1)/2)+1 x floor((W-1)/2)+1, for `planes` dense H x W planes (any H, W >= 1);
+ *   pair_moments: for two dense [N][C][HW] maps, per (n, c): out[n*out_bs + c*5 + {0..4}] = mu_x, mu_y, var_x, var_y, cov_xy (fp64;
+ *                 var = mean((x - mu)^2), cov = mean(x y) - mu_x mu_y).  Fixed-order split-plane partials in `workspace`
+ *                 (dcvic_pair_moments_workspace_doubles(N*C, HW) doubles) then a finishing pass: bitwise reproducible, batch-invariant;
+ *   dists_score:  out[n] = 1 - (sum_c alpha[c] S1 + sum_c beta[c] S2) over the C = 1475 concatenated channels of the 6 taps, in order,
+ *                 S1 = (2 mu_x mu_y + 1e-6) / (mu_x^2 + mu_y^2 + 1e-6), S2 = (2 cov + 1e-6) / (var_x + var_y + 1e-6), alpha and beta
+ *                 already divided by (sum alpha + sum beta); C <= 2048;
+ *   lpips_score:  out[n] = sum_k mom[(n*taps + k)*5] -- LPIPS: the sum over taps of the spatial mean of dcvic_lpips_tap_f32's per-pixel
+ *                 map (its mean taken by pair_moments as a 1-channel plane with f1 == f0, which reads the plane once).
+ * pair_moments launches the planes in groups of at most 65535 (grid.y), so any N * C is served. */
+int dcvic_l2pool_f32(const float* x, float* y, long long planes, int H, int W, void* stream);
+long long dcvic_pair_moments_workspace_doubles(long long planes, long long HW);
+int dcvic_pair_moments_f64(const float* f0, const float* f1, int N, int C, long long HW, double* out, long long out_bs, double* workspace,
+                           void* stream);
+int dcvic_dists_score_f64(const double* mom, long long mom_bs, const double* alpha, const double* beta, int N, int C, double* out,
+                          void* stream);
+int dcvic_lpips_score_f64(const double* mom, int N, int taps, double* out, void* stream);
 
 #ifdef __cplusplus
 }

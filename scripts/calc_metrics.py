@@ -6,10 +6,16 @@ Same flags (--real_dir --fake_dir -d/--device) and the same output file `<fake_d
   * "bpp"  : read from `<fake_dir>/_avg_bitrate.json`, which scripts/compress.py wrote (calc_metrics.py:322-327);
   * "PSNR" : image-averaged PSNR over the sorted, name-matched *.png pairs, on RGB float32 in [0, 255]:
              20 log10(255) - 10 log10(mean squared error)  (calc_metrics.py:121-171), threads over images.
-FID, LPIPS and DISTS (calc_metrics.py:174-320) need pretrained Inception / AlexNet / DISTS weights that the reference
-downloads at first use; there is no network here, so they are skipped with a message (and absent from the json) unless
-the packages AND their weights are importable.  The HiFiC FID patch cropper is provided (`crop_hific_fid_patches`,
-calc_metrics.py:307-320) because the patch sets it produces are what an external FID tool consumes.
+  * "LPIPS": with --lpips_path (a state dict of lpips.LPIPS(net='alex'), as scripts/train.py takes): LPIPS(fake, real) per image
+             on RGB in [-1, 1] (ToTensor, Normalize(.5, .5)), computed by dc_vic_amd.metrics on the device -d (calc_metrics.py:174-196);
+  * "DISTS": with --dists_path (a complete DISTS() state dict, or DISTS_pytorch's weights.pt {alpha, beta} plus --vgg16_path,
+             torchvision's VGG16 state dict): DISTS(fake, real) per image on RGB in [0, 1] (ToTensor) (calc_metrics.py:198-215).
+  Both are image means of per-image values at full resolution; images are batched by shape, and a value does not depend on its batch.
+  Weight files are loaded (torch.load weights_only=True) and checked before any image is read.  Parity with the lpips / DISTS_pytorch
+  packages is unpinned (restated architectures; see dc_vic_amd/metrics.py).
+A metric whose weights are not given is skipped with a message and absent from the json; without these flags nothing here touches
+torch or the GPU.  FID needs Inception weights and is always skipped.  The HiFiC FID patch cropper is provided
+(`crop_hific_fid_patches`, calc_metrics.py:307-320) because the patch sets it produces are what an external FID tool consumes.
 """
 from __future__ import annotations
 
@@ -19,9 +25,11 @@ import os
 import sys
 from concurrent.futures import ThreadPoolExecutor
 from glob import glob
-from typing import List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
+
+sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
 def get_real_fake_path_list(real_dir: str, fake_dir: str) -> Tuple[List[str], List[str]]:
@@ -77,18 +85,80 @@ def retrieve_bitrate(fake_dir: str) -> float:
         return json.load(f)["avg_bpp"]
 
 
+# images per call: as many same-shape pairs as fit this many pixels, at most MAX_BATCH_IMAGES (at least one); x and y run as a batch of
+# twice that.  Values do not depend on the batch (the kernels are batch-invariant), so these only bound memory and launch sizes.
+MAX_BATCH_PIXELS = 1 << 22
+MAX_BATCH_IMAGES = 16
+
+
+def load_metric_models(lpips_path: Optional[str], dists_path: Optional[str], vgg16_path: Optional[str]) -> Dict[str, object]:
+    """The networks of the metrics whose weights were given, on the host ({} without any: torch is not imported then)."""
+    if vgg16_path and not dists_path:
+        raise ValueError("--vgg16_path is only used by DISTS: give --dists_path (DISTS_pytorch's weights.pt) with it")
+    models: Dict[str, object] = {}
+    if lpips_path:
+        import torch
+        from dc_vic_amd.metrics import load_lpips
+        models["LPIPS"] = load_lpips(torch.load(lpips_path, map_location="cpu", weights_only=True))
+    if dists_path:
+        from dc_vic_amd.metrics import DISTSVGG
+        models["DISTS"] = DISTSVGG.from_files(vgg16_path=vgg16_path, dists_path=dists_path)
+    return models
+
+
+def perceptual_metrics(models: Dict[str, object], real_paths: List[str], fake_paths: List[str], device: str) -> Dict[str, float]:
+    """Image means of the per-image LPIPS / DISTS values, each computed as metric(fake, real) on the device."""
+    import torch
+    from PIL import Image
+    from dc_vic_amd import metrics as M
+    dev = torch.device(device)
+    torch.cuda.set_device(dev)
+    for m in models.values():
+        m.to(dev)
+    buckets: Dict[Tuple[int, ...], List[int]] = {}
+    for i, r in enumerate(real_paths):
+        with Image.open(r) as im:
+            buckets.setdefault((im.height, im.width), []).append(i)
+    vals = {k: np.zeros(len(real_paths), dtype=np.float64) for k in models}
+    for (H, W), idx in buckets.items():
+        per = max(1, min(MAX_BATCH_IMAGES, MAX_BATCH_PIXELS // (H * W)))
+        for b0 in range(0, len(idx), per):
+            ids = idx[b0:b0 + per]
+            real = np.stack([read_img(real_paths[i]) for i in ids])
+            fake = np.stack([read_img(fake_paths[i]) for i in ids])
+            assert real.shape == fake.shape, [fake_paths[i] for i in ids]
+            # ToTensor: uint8 / 255 in fp32, HWC -> CHW
+            r01 = np.ascontiguousarray((real / np.float32(255.0)).transpose(0, 3, 1, 2))
+            f01 = np.ascontiguousarray((fake / np.float32(255.0)).transpose(0, 3, 1, 2))
+            if "LPIPS" in models:                 # Normalize(.5, .5)
+                fx = torch.from_numpy((f01 - np.float32(0.5)) / np.float32(0.5)).to(dev)
+                rx = torch.from_numpy((r01 - np.float32(0.5)) / np.float32(0.5)).to(dev)
+                vals["LPIPS"][ids] = M.lpips(models["LPIPS"], fx, rx).cpu().numpy()
+            if "DISTS" in models:
+                vals["DISTS"][ids] = M.dists(models["DISTS"], torch.from_numpy(f01).to(dev), torch.from_numpy(r01).to(dev)).cpu().numpy()
+    return {k: float(np.mean(v)) for k, v in vals.items()}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--real_dir", type=str, required=True)
     ap.add_argument("--fake_dir", type=str, required=True)
-    ap.add_argument("-d", "--device", type=str, default="cuda:0")     # kept for flag compatibility; PSNR runs on the host
+    ap.add_argument("-d", "--device", type=str, default="cuda:0")     # LPIPS / DISTS run here; PSNR runs on the host
+    ap.add_argument("--lpips_path", type=str, default=None, help="state dict of lpips.LPIPS(net='alex') (torch.save'd; weights_only load)")
+    ap.add_argument("--dists_path", type=str, default=None,
+                    help="DISTS_pytorch weights.pt ({alpha, beta}; needs --vgg16_path) or a complete DISTS() state dict")
+    ap.add_argument("--vgg16_path", type=str, default=None, help="torchvision VGG16 ImageNet state dict (features.*) for --dists_path")
     a = ap.parse_args(argv)
+    models = load_metric_models(a.lpips_path, a.dists_path, a.vgg16_path)
     out = {"bpp": retrieve_bitrate(a.fake_dir)}
     real, fake = get_real_fake_path_list(a.real_dir, a.fake_dir)
     out["PSNR"] = average_psnr(real, fake)
     print(f"{len(real)} images: PSNR: {out['PSNR']:.4}")
+    if models:
+        out.update(perceptual_metrics(models, real, fake, a.device))
     for name in ("FID", "LPIPS", "DISTS"):
-        print(f"[calc_metrics] {name} skipped: its pretrained network weights cannot be fetched offline", file=sys.stderr)
+        if name not in models:
+            print(f"[calc_metrics] {name} skipped: its pretrained network weights cannot be fetched offline", file=sys.stderr)
     with open(os.path.join(a.fake_dir, "_metrics.json"), "w") as f:
         json.dump(out, f, indent=4)
     print(f"Results: {a.fake_dir}")

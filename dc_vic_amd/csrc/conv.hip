@@ -428,42 +428,86 @@ extern "C" int dcvic_conv_select_class(const dcvic_conv_desc* d, int N, int Hout
     return best_cls;
 }
 
-extern "C" int dcvic_conv2d_f32(const dcvic_conv_desc* d, const float* packed, const dcvic_conv_io* io, void* stream) {
-    DCVIC_CHECK_ARG(d && packed && io && io->out, "conv2d: null pointer");
-    DCVIC_CHECK_ARG(io->n_src >= 1 && io->n_src <= DCVIC_MAX_SRC, "conv2d: n_src %d", io->n_src);
+int dcvic_conv_check_io(const DcvicConvRules& r, const void* weights, const dcvic_conv_io* io, ConvKArgs* K) {
+    const char* nm = r.name;
+    DCVIC_CHECK_ARG(io && io->out && weights && r.Cin > 0 && r.Cout > 0, "%s: null pointer", nm);
+    DCVIC_CHECK_ARG(io->n_src >= 1 && io->n_src <= r.max_src, "%s: n_src %d (1..%d)", nm, io->n_src, r.max_src);
+    DCVIC_CHECK_ARG(io->N > 0 && io->H > 0 && io->W > 0 && io->Hout > 0 && io->Wout > 0, "%s: bad sizes", nm);
+    auto vec16 = [&](const void* p, long long bs) { return !r.vec16 || ((reinterpret_cast<uintptr_t>(p) & 15) == 0 && (bs & 3) == 0); };
     int csum = 0;
     for (int i = 0; i < io->n_src; ++i) {
-        DCVIC_CHECK_ARG(io->src[i].ptr && io->src[i].C > 0, "conv2d: source %d empty", i);
-        DCVIC_CHECK_ARG(io->src[i].batch_stride >= (long long)io->src[i].C * io->H * io->W, "conv2d: source %d batch stride too small", i);
-        csum += io->src[i].C;
+        const dcvic_src& s = io->src[i];
+        DCVIC_CHECK_ARG(s.ptr && s.C > 0 && s.C % r.src_cmul == 0, "%s: source %d empty or not a multiple of %d channels", nm, i, r.src_cmul);
+        DCVIC_CHECK_ARG(s.batch_stride >= (long long)s.C * io->H * io->W, "%s: source %d batch stride too small", nm, i);
+        DCVIC_CHECK_ARG(vec16(s.ptr, s.batch_stride), "%s: source %d must be a 16-byte aligned view", nm, i);
+        csum += s.C;
     }
-    DCVIC_CHECK_ARG(csum == d->Cin, "conv2d: sources carry %d channels, layer expects %d", csum, d->Cin);
-    DCVIC_CHECK_ARG(io->N > 0 && io->H > 0 && io->W > 0 && io->Hout > 0 && io->Wout > 0, "conv2d: bad sizes");
-    DCVIC_CHECK_ARG(io->osy >= 1 && io->osx >= 1 && io->ooy >= 0 && io->oox >= 0, "conv2d: bad output scatter");
-    DCVIC_CHECK_ARG((io->Hout - 1) * io->osy + io->ooy < io->Hfull && (io->Wout - 1) * io->osx + io->oox < io->Wfull,
-                    "conv2d: output scatter exceeds the output plane");
-    DCVIC_CHECK_ARG(io->out_batch_stride >= (long long)d->Cout * io->Hfull * io->Wfull, "conv2d: out batch stride too small");
-    DCVIC_CHECK_ARG((long long)io->H * io->W < (1ll << 30) && (long long)io->Hfull * io->Wfull < (1ll << 30), "conv2d: plane too large");
-    DCVIC_CHECK_ARG(!io->res || io->res_batch_stride >= (long long)d->Cout * io->Hfull * io->Wfull, "conv2d: res batch stride too small");
-    DCVIC_CHECK_ARG((io->aff_scale == nullptr) == (io->aff_shift == nullptr), "conv2d: affine needs both scale and shift");
-    DCVIC_CHECK_ARG(!io->init || io->init_batch_stride >= (long long)d->Cout * io->Hfull * io->Wfull, "conv2d: init batch stride too small");
+    DCVIC_CHECK_ARG(csum == r.Cin, "%s: sources carry %d channels, layer expects %d", nm, csum, r.Cin);
+    if (r.out_geom == DCVIC_OUT_SCATTER) {
+        DCVIC_CHECK_ARG(io->osy >= 1 && io->osx >= 1 && io->ooy >= 0 && io->oox >= 0, "%s: bad output scatter", nm);
+        DCVIC_CHECK_ARG((io->Hout - 1) * io->osy + io->ooy < io->Hfull && (io->Wout - 1) * io->osx + io->oox < io->Wfull,
+                        "%s: output scatter exceeds the output plane", nm);
+    } else {
+        const int f = r.out_geom == DCVIC_OUT_X2 ? 2 : 1;
+        DCVIC_CHECK_ARG(io->Hout == f * io->H && io->Wout == f * io->W && io->Hfull == io->Hout && io->Wfull == io->Wout && io->osy == 1 &&
+                        io->osx == 1 && io->ooy == 0 && io->oox == 0, "%s: output must be the %d x %d plane", nm, f * io->H, f * io->W);
+    }
+    DCVIC_CHECK_ARG(!r.max_plane || ((long long)io->H * io->W < r.max_plane &&
+                                     (r.out_geom != DCVIC_OUT_SCATTER || (long long)io->Hfull * io->Wfull < r.max_plane)),
+                    "%s: plane too large", nm);
+    const long long out_min = (long long)r.Cout * io->Hfull * io->Wfull;
+    DCVIC_CHECK_ARG(io->out_batch_stride >= out_min, "%s: output batch stride too small", nm);
+    DCVIC_CHECK_ARG(vec16(io->out, io->out_batch_stride), "%s: output must be a 16-byte aligned view", nm);
+    DCVIC_CHECK_ARG(!io->res || io->res_batch_stride >= out_min, "%s: residual batch stride too small", nm);
+    DCVIC_CHECK_ARG(!io->res || vec16(io->res, io->res_batch_stride), "%s: residual must be a 16-byte aligned view", nm);
+    if (r.affine) DCVIC_CHECK_ARG(!io->aff_scale == !io->aff_shift, "%s: affine needs both scale and shift", nm);
+    else DCVIC_CHECK_ARG(!io->aff_scale && !io->aff_shift, "%s: affine epilogue not supported", nm);
+    if (r.init) DCVIC_CHECK_ARG(!io->init || io->init_batch_stride >= out_min, "%s: init batch stride too small", nm);
+    else DCVIC_CHECK_ARG(!io->init, "%s: init accumulators not supported", nm);
+    if (!K) return DCVIC_OK;
+    memset(K, 0, sizeof(*K));
+    K->Cin = r.Cin; K->Cout = r.Cout; K->T = 9; K->stride = 1;
+    K->N = io->N; K->H = io->H; K->W = io->W; K->Hout = io->Hout; K->Wout = io->Wout; K->Hfull = io->Hfull; K->Wfull = io->Wfull;
+    K->osy = io->osy; K->osx = io->osx; K->ooy = io->ooy; K->oox = io->oox;
+    for (int i = 0; i < DCVIC_MAX_SRC; ++i) {
+        if (i < io->n_src) { K->src[i] = io->src[i].ptr; K->srcC[i] = io->src[i].C; K->src_bs[i] = io->src[i].batch_stride; }
+        else { K->src[i] = io->src[0].ptr; K->srcC[i] = 1 << 30; K->src_bs[i] = 0; }
+    }
+    K->out = io->out; K->out_bs = io->out_batch_stride; K->bias = io->bias; K->act = io->act;
+    K->res = io->res; K->res_bs = io->res_batch_stride;
+    if (r.affine) { K->affs = io->aff_scale; K->afft = io->aff_shift; K->aff_bs = io->aff_batch_stride; }
+    if (r.init) { K->init = io->init; K->init_bs = io->init_batch_stride; }
+    K->wp = static_cast<const float*>(weights);
+    return DCVIC_OK;
+}
+
+int dcvic_conv_tiles(const char* name, ConvKArgs* K, int kc, int co, int th, int tw) {
+    K->n_chunks = dcvic_cdiv(K->Cin, kc);
+    K->n_cotiles = dcvic_cdiv(K->Cout, co);
+    K->tiles_y = dcvic_cdiv(K->Hout, th);
+    K->tiles_x = dcvic_cdiv(K->Wout, tw);
+    const long long blocks = (long long)K->N * K->tiles_y * K->tiles_x * K->n_cotiles;
+    DCVIC_CHECK_ARG(blocks < (1ll << 31), "%s: grid too large", name);
+    K->nblocks = (int)blocks;
+    return DCVIC_OK;
+}
+
+int dcvic_persistent_grid(long long nblocks) {
+    int grid = (dcvic_num_cu() / NXCD) * NXCD;
+    if (grid < NXCD) grid = NXCD;
+    if ((long long)grid > nblocks) grid = (int)((nblocks + NXCD - 1) / NXCD) * NXCD;
+    return grid;
+}
+
+extern "C" int dcvic_conv2d_f32(const dcvic_conv_desc* d, const float* packed, const dcvic_conv_io* io, void* stream) {
+    DCVIC_CHECK_ARG(d, "conv2d: null pointer");
     const int cls = d->cfg;
     DCVIC_CHECK_ARG(cls >= 0 && cls <= 3, "conv2d: bad cfg %d", cls);
-    init_num_cu();
-
+    const DcvicConvRules rules = {"conv2d", d->Cin, d->Cout, DCVIC_MAX_SRC, 1, false, DCVIC_OUT_SCATTER, true, true, 1ll << 30};
     ConvKArgs K;
-    memset(&K, 0, sizeof(K));
-    K.Cin = d->Cin; K.Cout = d->Cout; K.T = d->T; K.stride = d->stride;
-    K.N = io->N; K.H = io->H; K.W = io->W; K.Hout = io->Hout; K.Wout = io->Wout; K.Hfull = io->Hfull; K.Wfull = io->Wfull;
-    K.osy = io->osy; K.osx = io->osx; K.ooy = io->ooy; K.oox = io->oox;
-    for (int i = 0; i < DCVIC_MAX_SRC; ++i) {
-        if (i < io->n_src) { K.src[i] = io->src[i].ptr; K.srcC[i] = io->src[i].C; K.src_bs[i] = io->src[i].batch_stride; }
-        else { K.src[i] = io->src[0].ptr; K.srcC[i] = 1 << 30; K.src_bs[i] = 0; }
-    }
-    K.out = io->out; K.out_bs = io->out_batch_stride; K.bias = io->bias; K.act = io->act;
-    K.res = io->res; K.res_bs = io->res_batch_stride; K.affs = io->aff_scale; K.afft = io->aff_shift; K.aff_bs = io->aff_batch_stride;
-    K.wp = packed;
-    K.init = io->init; K.init_bs = io->init_batch_stride;
+    if (const int rc = dcvic_conv_check_io(rules, packed, io, &K)) return rc;
+    init_num_cu();
+    K.T = d->T; K.stride = d->stride;
     int dy_min = 127, dy_max = -128, dx_min = 127, dx_max = -128;
     // taps must form a regular grid (true for every conv / transposed-conv phase the desc builders emit)
     {
@@ -490,13 +534,10 @@ extern "C" int dcvic_conv2d_f32(const dcvic_conv_desc* d, const float* packed, c
         K.halves = fam ? 2 : 1;
     }
     const int TC = cfg_TC(cls);
-    K.n_chunks = n_chunks_of(d);
-    K.n_cotiles = n_cotiles_of(d);
     // tile width: the largest power of two <= 32 that does not exceed the (rounded-up) output width
     const int TWlog = tile_width_log(io->Wout);
     const int TW = 1 << TWlog;
     K.TWlog = TWlog;
-    K.tiles_x = (io->Wout + TW - 1) / TW;
     // pixel-tile size by the occupancy / tile-efficiency score shared with dcvic_conv_select_class
     int P = 0;
     {
@@ -511,7 +552,7 @@ extern "C" int dcvic_conv2d_f32(const dcvic_conv_desc* d, const float* packed, c
 #endif
     DCVIC_CHECK_ARG(P > 0, "conv2d: no tile variant fits");
     const int TH = P / TW;
-    K.tiles_y = (io->Hout + TH - 1) / TH;
+    if (const int rc = dcvic_conv_tiles("conv2d", &K, KC, TC, TH, TW)) return rc;
     if (d->upsample) {
         K.PH = TH / 2 + ((dy_max - dy_min + 1) >> 1) + 1;
         K.PW = TW / 2 + ((dx_max - dx_min + 1) >> 1) + 1;
@@ -539,9 +580,7 @@ extern "C" int dcvic_conv2d_f32(const dcvic_conv_desc* d, const float* packed, c
     const int slabs = (TG == d->T) ? CPS * d->T : TG;
     const size_t lds = (size_t)(((CPS * KC * K.plane + 3) & ~3) + slabs * KC * TC) * sizeof(float);
     DCVIC_CHECK_ARG(lds <= 160 * 1024, "conv2d: LDS %zu too large", lds);
-    const long long blocks = (long long)io->N * K.tiles_y * K.tiles_x * K.n_cotiles;
-    DCVIC_CHECK_ARG(blocks < (1ll << 31), "conv2d: grid too large");
-    K.nblocks = (int)blocks;
+    const long long blocks = K.nblocks;
     hipStream_t st = (hipStream_t)stream;
     const bool ups = d->upsample != 0;
     if (P == 256 && g_use_dma) {

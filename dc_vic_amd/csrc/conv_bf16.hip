@@ -258,44 +258,18 @@ extern "C" int dcvic_conv3x3_bf16_pack_f32(const float* w, void* packed, int Cin
 }
 
 extern "C" int dcvic_conv3x3_bf16_f32(int Cin, int Cout, int upsample, const void* packed, const dcvic_conv_io* io, void* stream) {
-    DCVIC_CHECK_ARG(packed && io && io->out && Cin > 0 && Cout > 0, "conv3x3_bf16: null pointer");
-    DCVIC_CHECK_ARG(io->n_src >= 1 && io->n_src <= DCVIC_MAX_SRC, "conv3x3_bf16: n_src %d", io->n_src);
-    DCVIC_CHECK_ARG(io->N > 0 && io->H > 0 && io->W > 0, "conv3x3_bf16: bad sizes");
-    const int Ho = upsample ? 2 * io->H : io->H, Wo = upsample ? 2 * io->W : io->W;
-    int csum = 0;
-    for (int i = 0; i < io->n_src; ++i) {
-        DCVIC_CHECK_ARG(io->src[i].ptr && io->src[i].C > 0 && io->src[i].C % 8 == 0, "conv3x3_bf16: source %d needs a multiple of 8 channels", i);
-        DCVIC_CHECK_ARG(io->src[i].batch_stride >= (long long)io->src[i].C * io->H * io->W, "conv3x3_bf16: source %d batch stride too small", i);
-        csum += io->src[i].C;
-    }
-    DCVIC_CHECK_ARG(csum == Cin, "conv3x3_bf16: sources carry %d channels, layer expects %d", csum, Cin);
-    DCVIC_CHECK_ARG(io->Hout == Ho && io->Wout == Wo && io->Hfull == Ho && io->Wfull == Wo && io->osy == 1 && io->osx == 1 &&
-                    io->ooy == 0 && io->oox == 0, "conv3x3_bf16: stride-1 pad-1 geometry only (output %d x %d)", Ho, Wo);
-    DCVIC_CHECK_ARG(!io->init, "conv3x3_bf16: init accumulators are not supported");
-    DCVIC_CHECK_ARG(io->out_batch_stride >= (long long)Cout * Ho * Wo, "conv3x3_bf16: output batch stride too small");
-    DCVIC_CHECK_ARG(!io->res || io->res_batch_stride >= (long long)Cout * Ho * Wo, "conv3x3_bf16: residual batch stride too small");
-    DCVIC_CHECK_ARG(!io->aff_scale == !io->aff_shift, "conv3x3_bf16: affine needs both scale and shift");
+    const DcvicConvRules rules = {"conv3x3_bf16", Cin, Cout, DCVIC_MAX_SRC, 8, false, upsample ? DCVIC_OUT_X2 : DCVIC_OUT_SAME, true, false, 0};
+    ConvKArgs K;   // the epilogue's view of the launch (conv_common.h)
+    if (const int rc = dcvic_conv_check_io(rules, packed, io, &K)) return rc;
+    if (const int rc = dcvic_conv_tiles("conv3x3_bf16", &K, BF_KC, BF_CO, BF_TH, BF_TW)) return rc;
     Bf16Args A;
     memset(&A, 0, sizeof(A));
-    A.Cin = Cin; A.Cout = Cout; A.N = io->N; A.H = io->H; A.W = io->W; A.Ho = Ho; A.Wo = Wo;
-    for (int i = 0; i < DCVIC_MAX_SRC; ++i) {
-        if (i < io->n_src) { A.src[i] = io->src[i].ptr; A.srcC[i] = io->src[i].C; A.src_bs[i] = io->src[i].batch_stride; }
-        else { A.src[i] = io->src[0].ptr; A.srcC[i] = 1 << 30; A.src_bs[i] = 0; }
-    }
+    A.Cin = Cin; A.Cout = Cout; A.N = K.N; A.H = K.H; A.W = K.W; A.Ho = K.Hout; A.Wo = K.Wout;
+    for (int i = 0; i < DCVIC_MAX_SRC; ++i) { A.src[i] = K.src[i]; A.srcC[i] = K.srcC[i]; A.src_bs[i] = K.src_bs[i]; }
     A.wp = (const unsigned short*)packed;
-    A.n_chunks = (Cin + BF_KC - 1) / BF_KC;
-    A.tiles_x = dcvic_cdiv(Wo, BF_TW); A.tiles_y = dcvic_cdiv(Ho, BF_TH); A.co_tiles = dcvic_cdiv(Cout, BF_CO);
-    const long long blocks = (long long)A.N * A.tiles_y * A.tiles_x * A.co_tiles;
-    DCVIC_CHECK_ARG(blocks < (1ll << 31), "conv3x3_bf16: grid too large");
-    // the epilogue's view of the launch (conv_common.h)
-    ConvKArgs K;
-    memset(&K, 0, sizeof(K));
-    K.Cin = Cin; K.Cout = Cout; K.N = io->N; K.Hout = Ho; K.Wout = Wo; K.Hfull = Ho; K.Wfull = Wo;
-    K.out = io->out; K.out_bs = io->out_batch_stride; K.bias = io->bias; K.act = io->act;
-    K.res = io->res; K.res_bs = io->res_batch_stride;
-    K.affs = io->aff_scale; K.afft = io->aff_shift; K.aff_bs = io->aff_batch_stride;
-    if (upsample) conv3x3_bf16_kernel<true><<<(unsigned)blocks, NTHREADS, 0, (hipStream_t)stream>>>(A, K);
-    else conv3x3_bf16_kernel<false><<<(unsigned)blocks, NTHREADS, 0, (hipStream_t)stream>>>(A, K);
+    A.n_chunks = K.n_chunks; A.tiles_x = K.tiles_x; A.tiles_y = K.tiles_y; A.co_tiles = K.n_cotiles;
+    if (upsample) conv3x3_bf16_kernel<true><<<(unsigned)K.nblocks, NTHREADS, 0, (hipStream_t)stream>>>(A, K);
+    else conv3x3_bf16_kernel<false><<<(unsigned)K.nblocks, NTHREADS, 0, (hipStream_t)stream>>>(A, K);
     DCVIC_CHECK_LAUNCH("conv3x3_bf16");
     return DCVIC_OK;
 }

@@ -1,4 +1,4 @@
-// Shared between conv.hip (generic implicit-GEMM kernel) and conv3x3.hip (DMA double-buffered 3x3 kernel).
+// Shared by the convolution translation units: the kernel argument block, the epilogue, and the host-side io check every entry point uses.
 #pragma once
 #include "common.h"
 
@@ -103,6 +103,33 @@ __device__ __forceinline__ void dcvic_epilogue_dispatch(const ConvKArgs& K, F&& 
         if (K.affs) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{});
     }
 }
+
+// What one convolution entry point accepts in a dcvic_conv_io.  Every entry point also needs: io, io->out and the weights non-null,
+// Cin, Cout > 0, 1..max_src non-empty sources whose channels sum to Cin, N, H, W, Hout, Wout > 0, and batch strides of at least
+// C x plane for the sources, out, res and init.
+enum { DCVIC_OUT_SCATTER, DCVIC_OUT_SAME, DCVIC_OUT_X2 };
+struct DcvicConvRules {
+    const char* name;    // error prefix
+    int Cin, Cout;
+    int max_src;
+    int src_cmul;        // every source's channel count is a multiple of this
+    bool vec16;          // sources, out and res are 16-byte aligned with batch strides a multiple of 4 floats
+    int out_geom;        // DCVIC_OUT_SCATTER: dcvic_conv2d_f32's (osy, osx, ooy, oox) scatter into Hfull x Wfull;
+                         // DCVIC_OUT_SAME / _X2: Hout = Hfull = H (2H), Wout = Wfull = W (2W), no scatter
+    bool affine;         // affine epilogue allowed (then only with both vectors)
+    bool init;           // init accumulators allowed
+    long long max_plane; // H x W (and, for the scatter, Hfull x Wfull) stays below this; 0: no limit
+};
+
+// defined in conv.hip.  Checks io against r; when K is not null, fills every ConvKArgs field that comes from io and the weights
+// (T = 9, stride = 1; unused source slots padded with srcC = 2^30; affine / init only where r allows them; everything else 0).
+// Returns DCVIC_OK, or DCVIC_EINVAL with the error set.
+int dcvic_conv_check_io(const DcvicConvRules& r, const void* weights, const dcvic_conv_io* io, ConvKArgs* K);
+// defined in conv.hip.  K->n_chunks / n_cotiles / tiles_y / tiles_x for kc-channel chunks, co-channel tiles and th x tw output tiles
+// of K->Hout x K->Wout, and K->nblocks = N x tiles_y x tiles_x x n_cotiles.  DCVIC_EINVAL past 2^31 - 1 workgroups.
+int dcvic_conv_tiles(const char* name, ConvKArgs* K, int kc, int co, int th, int tw);
+// defined in conv.hip.  Grid of a persistent kernel: one workgroup per CU, a multiple of the 8 XCDs, no more than nblocks needs.
+int dcvic_persistent_grid(long long nblocks);
 
 // defined in conv3x3.hip: returns DCVIC_OK after launching, or 1 if the layer is not eligible
 int dcvic_try_conv3x3_dma(const ConvKArgs& K, int n_src, bool upsample, int cls, hipStream_t st, int* variant_out);

@@ -12,7 +12,7 @@
 //     its 4 pixels for the 4 channels in registers (24 ds_read_b128) and runs 36 x CO x 4 fmaf on it, weights as LDS broadcasts.
 //   * thin_cin_kernel<CI>: Cin = CI <= 4.  4 pixels per thread: their 3 x 6 x CI input values live in registers, then per output
 //     channel one fmaf chain per pixel (weights through the scalar cache) and one 16-byte store (1 KiB per wave-instruction).
-#include "common.h"
+#include "conv_common.h"
 #include <type_traits>
 
 struct ThinArgs {
@@ -254,26 +254,19 @@ extern "C" int dcvic_conv3x3_thin_applies(int Cin, int Cout) {
 }
 
 extern "C" int dcvic_conv3x3_thin_f32(const float* w, int Cin, int Cout, const dcvic_conv_io* io, void* stream) {
-    DCVIC_CHECK_ARG(w && io && io->out, "conv3x3_thin: null pointer");
     DCVIC_CHECK_ARG(dcvic_conv3x3_thin_applies(Cin, Cout), "conv3x3_thin: Cin %d / Cout %d is not a thin layer", Cin, Cout);
-    DCVIC_CHECK_ARG(io->n_src == 1 && io->src[0].ptr && io->src[0].C == Cin, "conv3x3_thin: one source with Cin channels");
-    DCVIC_CHECK_ARG(io->N > 0 && io->H > 0 && io->W > 0, "conv3x3_thin: bad sizes");
-    DCVIC_CHECK_ARG(io->Hout == io->H && io->Wout == io->W && io->Hfull == io->H && io->Wfull == io->W && io->osy == 1 && io->osx == 1 &&
-                    io->ooy == 0 && io->oox == 0, "conv3x3_thin: stride-1 pad-1 geometry only");
-    DCVIC_CHECK_ARG(!io->aff_scale && !io->aff_shift && !io->init, "conv3x3_thin: affine / init epilogues are not supported");
-    const long long HW = (long long)io->H * io->W;
-    DCVIC_CHECK_ARG(io->src[0].batch_stride >= (long long)Cin * HW && io->out_batch_stride >= (long long)Cout * HW, "conv3x3_thin: batch stride too small");
-    DCVIC_CHECK_ARG(!io->res || io->res_batch_stride >= (long long)Cout * HW, "conv3x3_thin: residual batch stride too small");
+    const DcvicConvRules rules = {"conv3x3_thin", Cin, Cout, 1, 1, false, DCVIC_OUT_SAME, false, false, 0};
+    if (const int rc = dcvic_conv_check_io(rules, w, io, nullptr)) return rc;
     ThinArgs A;
     A.x = io->src[0].ptr; A.x_bs = io->src[0].batch_stride; A.w = w; A.bias = io->bias; A.res = io->res; A.res_bs = io->res_batch_stride;
     A.out = io->out; A.out_bs = io->out_batch_stride; A.N = io->N; A.H = io->H; A.W = io->W; A.Cin = Cin; A.Cout = Cout; A.act = io->act;
     A.vec = (io->W % 4 == 0) && (reinterpret_cast<uintptr_t>(io->out) % 16 == 0) && (io->out_batch_stride % 4 == 0) &&
             (!io->res || ((reinterpret_cast<uintptr_t>(io->res) % 16 == 0) && (io->res_batch_stride % 4 == 0)));
+    A.tiles_x = dcvic_cdiv(io->W, TH_COLS); A.tiles_y = dcvic_cdiv(io->H, TH_ROWS);
+    const long long blocks = (long long)io->N * A.tiles_x * A.tiles_y;
+    DCVIC_CHECK_ARG(blocks < (1ll << 31), "conv3x3_thin: grid too large");
     hipStream_t st = (hipStream_t)stream;
     if (Cout <= 4 && Cin >= 8) {
-        A.tiles_x = dcvic_cdiv(io->W, TH_COLS); A.tiles_y = dcvic_cdiv(io->H, TH_ROWS);
-        const long long blocks = (long long)io->N * A.tiles_x * A.tiles_y;
-        DCVIC_CHECK_ARG(blocks < (1ll << 31), "conv3x3_thin: grid too large");
         switch (Cout) {
             case 1: thin_cout_kernel<1><<<(int)blocks, 256, 0, st>>>(A); break;
             case 2: thin_cout_kernel<2><<<(int)blocks, 256, 0, st>>>(A); break;
@@ -281,9 +274,6 @@ extern "C" int dcvic_conv3x3_thin_f32(const float* w, int Cin, int Cout, const d
             default: thin_cout_kernel<4><<<(int)blocks, 256, 0, st>>>(A); break;
         }
     } else {
-        A.tiles_x = dcvic_cdiv(io->W, TH_COLS); A.tiles_y = dcvic_cdiv(io->H, TH_ROWS);
-        const long long blocks = (long long)io->N * A.tiles_x * A.tiles_y;
-        DCVIC_CHECK_ARG(blocks < (1ll << 31), "conv3x3_thin: grid too large");
         switch (Cin) {
             case 1: thin_cin_kernel<1><<<(int)blocks, 256, 0, st>>>(A); break;
             case 2: thin_cin_kernel<2><<<(int)blocks, 256, 0, st>>>(A); break;

@@ -824,53 +824,15 @@ extern "C" int dcvic_wino_ups_pack_f32(const float* w, float* packed, int Cin, i
 }
 
 extern "C" int dcvic_conv3x3_wino_ups_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, void* stream) {
-    DCVIC_CHECK_ARG(packed && io && io->out && Cin > 0 && Cout > 0, "conv3x3_wino_ups: null pointer");
-    DCVIC_CHECK_ARG(io->n_src >= 1 && io->n_src <= DCVIC_MAX_SRC, "conv3x3_wino_ups: n_src %d", io->n_src);
-    int csum = 0;
-    for (int i = 0; i < io->n_src; ++i) {
-        DCVIC_CHECK_ARG(io->src[i].ptr && io->src[i].C > 0 && io->src[i].C % KC == 0, "conv3x3_wino_ups: source %d needs a multiple of 8 channels", i);
-        DCVIC_CHECK_ARG(io->src[i].batch_stride >= (long long)io->src[i].C * io->H * io->W, "conv3x3_wino_ups: source %d batch stride too small", i);
-        DCVIC_CHECK_ARG((reinterpret_cast<uintptr_t>(io->src[i].ptr) & 15) == 0 && (io->src[i].batch_stride & 3) == 0,
-                        "conv3x3_wino_ups: source %d must be 16-byte aligned", i);
-        csum += io->src[i].C;
-    }
-    DCVIC_CHECK_ARG(csum == Cin, "conv3x3_wino_ups: sources carry %d channels, layer expects %d", csum, Cin);
-    DCVIC_CHECK_ARG(io->N > 0 && io->H > 0 && io->W > 0 && (io->W & 3) == 0, "conv3x3_wino_ups: bad sizes (input width must be a multiple of 4)");
-    DCVIC_CHECK_ARG(io->Hfull == 2 * io->H && io->Wfull == 2 * io->W && io->Hout == io->Hfull && io->Wout == io->Wfull && io->osy == 1 && io->osx == 1 &&
-                    io->ooy == 0 && io->oox == 0, "conv3x3_wino_ups: output must be the x2 plane");
-    DCVIC_CHECK_ARG(!io->aff_scale && !io->aff_shift && !io->init, "conv3x3_wino_ups: affine / init epilogues are not supported");
-    DCVIC_CHECK_ARG((long long)io->H * io->W * KC < (1ll << 31), "conv3x3_wino_ups: plane too large");
-    const long long HWo = (long long)io->Hfull * io->Wfull;
-    DCVIC_CHECK_ARG(io->out_batch_stride >= (long long)Cout * HWo && (io->out_batch_stride & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(io->out) & 15) == 0, "conv3x3_wino_ups: output view must be 16-byte aligned");
-    DCVIC_CHECK_ARG(!io->res || (io->res_batch_stride >= (long long)Cout * HWo && (io->res_batch_stride & 3) == 0 &&
-                                 (reinterpret_cast<uintptr_t>(io->res) & 15) == 0), "conv3x3_wino_ups: residual view must be 16-byte aligned");
+    const DcvicConvRules rules = {"conv3x3_wino_ups", Cin, Cout, DCVIC_MAX_SRC, KC, true, DCVIC_OUT_X2, false, false, 1ll << 28};
     ConvKArgs K;
-    memset(&K, 0, sizeof(K));
-    K.Cin = Cin; K.Cout = Cout; K.T = 9; K.stride = 1;
-    K.N = io->N; K.H = io->H; K.W = io->W; K.Hout = io->Hfull; K.Wout = io->Wfull; K.Hfull = io->Hfull; K.Wfull = io->Wfull;
-    K.osy = K.osx = 1;
-    for (int i = 0; i < DCVIC_MAX_SRC; ++i) {
-        if (i < io->n_src) { K.src[i] = io->src[i].ptr; K.srcC[i] = io->src[i].C; K.src_bs[i] = io->src[i].batch_stride; }
-        else { K.src[i] = io->src[0].ptr; K.srcC[i] = 1 << 30; K.src_bs[i] = 0; }
-    }
-    K.out = io->out; K.out_bs = io->out_batch_stride; K.bias = io->bias; K.act = io->act;
-    K.res = io->res; K.res_bs = io->res_batch_stride;
-    K.wp = packed;
-    K.n_chunks = (Cin + KC - 1) / KC;
-    K.n_cotiles = (Cout + WN_CO - 1) / WN_CO;
-    K.tiles_y = (io->Hfull + WN_TH - 1) / WN_TH;
-    K.tiles_x = (io->Wfull + WN_TW - 1) / WN_TW;
-    const long long blocks = (long long)io->N * K.tiles_y * K.tiles_x * K.n_cotiles;
-    DCVIC_CHECK_ARG(blocks < (1ll << 31), "conv3x3_wino_ups: grid too large");
-    K.nblocks = (int)blocks;
+    if (const int rc = dcvic_conv_check_io(rules, packed, io, &K)) return rc;
+    DCVIC_CHECK_ARG((io->W & 3) == 0, "conv3x3_wino_ups: input width must be a multiple of 4");
+    if (const int rc = dcvic_conv_tiles("conv3x3_wino_ups", &K, KC, WN_CO, WN_TH, WN_TW)) return rc;
     static std::atomic<unsigned> attr_mask{0};
     if (DcvicAttrOnce once_{attr_mask})
         hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wino_ups_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    int grid = (dcvic_num_cu() / NXCD) * NXCD;
-    if (grid < NXCD) grid = NXCD;
-    if ((long long)grid > blocks) grid = (int)((blocks + NXCD - 1) / NXCD) * NXCD;
-    conv3x3_wino_ups_kernel<<<grid, WN_THREADS, WN_LDS_FLOATS * sizeof(float), (hipStream_t)stream>>>(K);
+    conv3x3_wino_ups_kernel<<<dcvic_persistent_grid(K.nblocks), WN_THREADS, WN_LDS_FLOATS * sizeof(float), (hipStream_t)stream>>>(K);
     DCVIC_CHECK_LAUNCH("conv3x3_wino_ups");
     return DCVIC_OK;
 }
@@ -890,49 +852,15 @@ extern "C" int dcvic_wino_pack_f32(const float* w, float* packed, int Cin, int C
 }
 
 extern "C" int dcvic_conv3x3_wino_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, void* stream) {
-    DCVIC_CHECK_ARG(packed && io && io->out && Cin > 0 && Cout > 0, "conv3x3_wino: null pointer");
-    DCVIC_CHECK_ARG(io->n_src >= 1 && io->n_src <= DCVIC_MAX_SRC, "conv3x3_wino: n_src %d", io->n_src);
-    int csum = 0;
-    for (int i = 0; i < io->n_src; ++i) {
-        DCVIC_CHECK_ARG(io->src[i].ptr && io->src[i].C > 0 && io->src[i].C % KC == 0, "conv3x3_wino: source %d needs a multiple of 8 channels", i);
-        DCVIC_CHECK_ARG(io->src[i].batch_stride >= (long long)io->src[i].C * io->H * io->W, "conv3x3_wino: source %d batch stride too small", i);
-        DCVIC_CHECK_ARG((reinterpret_cast<uintptr_t>(io->src[i].ptr) & 15) == 0 && (io->src[i].batch_stride & 3) == 0,
-                        "conv3x3_wino: source %d must be 16-byte aligned (16-byte LDS-DMA segments)", i);
-        csum += io->src[i].C;
-    }
-    DCVIC_CHECK_ARG(csum == Cin, "conv3x3_wino: sources carry %d channels, layer expects %d", csum, Cin);
-    DCVIC_CHECK_ARG(io->N > 0 && io->H > 0 && io->W > 0, "conv3x3_wino: bad sizes");
-    DCVIC_CHECK_ARG(io->Hout == io->H && io->Wout == io->W && io->Hfull == io->H && io->Wfull == io->W && io->osy == 1 && io->osx == 1 &&
-                    io->ooy == 0 && io->oox == 0, "conv3x3_wino: stride-1 pad-1 geometry only");
-    DCVIC_CHECK_ARG((io->W & 3) == 0, "conv3x3_wino: width must be a multiple of 4");
-    DCVIC_CHECK_ARG(!io->aff_scale && !io->aff_shift && !io->init, "conv3x3_wino: affine / init epilogues are not supported");
-    DCVIC_CHECK_ARG((long long)io->H * io->W * KC < (1ll << 31), "conv3x3_wino: plane too large");
-    DCVIC_CHECK_ARG(io->out_batch_stride >= (long long)Cout * io->H * io->W && (io->out_batch_stride & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(io->out) & 15) == 0, "conv3x3_wino: output view must be 16-byte aligned");
-    DCVIC_CHECK_ARG(!io->res || (io->res_batch_stride >= (long long)Cout * io->H * io->W && (io->res_batch_stride & 3) == 0 &&
-                                 (reinterpret_cast<uintptr_t>(io->res) & 15) == 0), "conv3x3_wino: residual view must be 16-byte aligned");
+    // 16-byte views: the input is staged in 16-byte LDS-DMA segments; plane limit: H x W x 8 < 2^31
+    const DcvicConvRules rules = {"conv3x3_wino", Cin, Cout, DCVIC_MAX_SRC, KC, true, DCVIC_OUT_SAME, false, false, 1ll << 28};
     ConvKArgs K;
-    memset(&K, 0, sizeof(K));
-    K.Cin = Cin; K.Cout = Cout; K.T = 9; K.stride = 1;
-    K.N = io->N; K.H = io->H; K.W = io->W; K.Hout = io->H; K.Wout = io->W; K.Hfull = io->H; K.Wfull = io->W;
-    K.osy = K.osx = 1;
-    for (int i = 0; i < DCVIC_MAX_SRC; ++i) {
-        if (i < io->n_src) { K.src[i] = io->src[i].ptr; K.srcC[i] = io->src[i].C; K.src_bs[i] = io->src[i].batch_stride; }
-        else { K.src[i] = io->src[0].ptr; K.srcC[i] = 1 << 30; K.src_bs[i] = 0; }
-    }
-    K.out = io->out; K.out_bs = io->out_batch_stride; K.bias = io->bias; K.act = io->act;
-    K.res = io->res; K.res_bs = io->res_batch_stride;
-    K.wp = packed;
+    if (const int rc = dcvic_conv_check_io(rules, packed, io, &K)) return rc;
+    DCVIC_CHECK_ARG((io->W & 3) == 0, "conv3x3_wino: width must be a multiple of 4");
 #ifdef DCVIC_WINO_EXPERIMENTS
     { const char* e = getenv("DCVIC_WINO_DEBUG"); K.TG = e ? atoi(e) : 0; }   // timing experiments only (wrong results)
 #endif
-    K.n_chunks = (Cin + KC - 1) / KC;
-    K.n_cotiles = (Cout + WN_CO - 1) / WN_CO;
-    K.tiles_y = (io->H + WN_TH - 1) / WN_TH;
-    K.tiles_x = (io->W + WN_TW - 1) / WN_TW;
-    const long long blocks = (long long)io->N * K.tiles_y * K.tiles_x * K.n_cotiles;
-    DCVIC_CHECK_ARG(blocks < (1ll << 31), "conv3x3_wino: grid too large");
-    K.nblocks = (int)blocks;
+    if (const int rc = dcvic_conv_tiles("conv3x3_wino", &K, KC, WN_CO, WN_TH, WN_TW)) return rc;
     static std::atomic<unsigned> attr_mask{0};
 #ifdef DCVIC_WINO_EXPERIMENTS
     const int dbg = K.TG >> 4;
@@ -945,11 +873,8 @@ extern "C" int dcvic_conv3x3_wino_f32(int Cin, int Cout, const float* packed, co
 #endif
     if (DcvicAttrOnce once_{attr_mask})
         hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wino_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    // persistent grid: one workgroup per CU (152 KiB of LDS each), a multiple of the 8 XCDs; each walks its share of the tiles
-    int grid = (dcvic_num_cu() / NXCD) * NXCD;
-    if (grid < NXCD) grid = NXCD;
-    if ((long long)grid > blocks) grid = (int)((blocks + NXCD - 1) / NXCD) * NXCD;
-    kern<<<grid, WN_THREADS, WN_LDS_FLOATS * sizeof(float), (hipStream_t)stream>>>(K);
+    // persistent grid (152 KiB of LDS per workgroup): each workgroup walks its share of the tiles
+    kern<<<dcvic_persistent_grid(K.nblocks), WN_THREADS, WN_LDS_FLOATS * sizeof(float), (hipStream_t)stream>>>(K);
     DCVIC_CHECK_LAUNCH("conv3x3_wino");
     return DCVIC_OK;
 }

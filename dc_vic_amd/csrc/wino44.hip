@@ -570,57 +570,20 @@ extern "C" int dcvic_conv3x3_wino44_stats_f32(int Cin, int Cout, const float* pa
 }
 
 static int wino44_launch(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream) {
-    DCVIC_CHECK_ARG(packed && io && io->out && Cin > 0 && Cout > 0, "conv3x3_wino44: null pointer");
-    DCVIC_CHECK_ARG(io->n_src >= 1 && io->n_src <= DCVIC_MAX_SRC, "conv3x3_wino44: n_src %d", io->n_src);
-    int csum = 0;
-    for (int i = 0; i < io->n_src; ++i) {
-        DCVIC_CHECK_ARG(io->src[i].ptr && io->src[i].C > 0 && io->src[i].C % F4_KC == 0, "conv3x3_wino44: source %d needs a multiple of 8 channels", i);
-        DCVIC_CHECK_ARG(io->src[i].batch_stride >= (long long)io->src[i].C * io->H * io->W, "conv3x3_wino44: source %d batch stride too small", i);
-        DCVIC_CHECK_ARG((reinterpret_cast<uintptr_t>(io->src[i].ptr) & 15) == 0 && (io->src[i].batch_stride & 3) == 0,
-                        "conv3x3_wino44: source %d must be 16-byte aligned (16-byte LDS-DMA segments)", i);
-        csum += io->src[i].C;
-    }
-    DCVIC_CHECK_ARG(csum == Cin, "conv3x3_wino44: sources carry %d channels, layer expects %d", csum, Cin);
-    DCVIC_CHECK_ARG(io->N > 0 && io->H > 0 && io->W > 0, "conv3x3_wino44: bad sizes");
-    DCVIC_CHECK_ARG(io->Hout == io->H && io->Wout == io->W && io->Hfull == io->H && io->Wfull == io->W && io->osy == 1 && io->osx == 1 &&
-                    io->ooy == 0 && io->oox == 0, "conv3x3_wino44: stride-1 pad-1 geometry only");
+    // 16-byte views: the input is staged in 16-byte LDS-DMA segments; plane limit: H x W x 8 < 2^31
+    const DcvicConvRules rules = {"conv3x3_wino44", Cin, Cout, DCVIC_MAX_SRC, F4_KC, true, DCVIC_OUT_SAME, false, false, 1ll << 28};
+    ConvKArgs K;
+    if (const int rc = dcvic_conv_check_io(rules, packed, io, &K)) return rc;
     DCVIC_CHECK_ARG((io->W & 3) == 0, "conv3x3_wino44: width must be a multiple of 4");
-    DCVIC_CHECK_ARG(!io->aff_scale && !io->aff_shift && !io->init, "conv3x3_wino44: affine / init epilogues are not supported");
     DCVIC_CHECK_ARG(io->act == DCVIC_ACT_NONE || io->act == DCVIC_ACT_RELU || io->act == DCVIC_ACT_LRELU02,
                     "conv3x3_wino44: activation %d not supported (none / ReLU / LeakyReLU(0.2) only)", io->act);
-    DCVIC_CHECK_ARG((long long)io->H * io->W * F4_KC < (1ll << 31), "conv3x3_wino44: plane too large");
-    DCVIC_CHECK_ARG(io->out_batch_stride >= (long long)Cout * io->H * io->W && (io->out_batch_stride & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(io->out) & 15) == 0, "conv3x3_wino44: output view must be 16-byte aligned");
-    DCVIC_CHECK_ARG(!io->res || (io->res_batch_stride >= (long long)Cout * io->H * io->W && (io->res_batch_stride & 3) == 0 &&
-                                 (reinterpret_cast<uintptr_t>(io->res) & 15) == 0), "conv3x3_wino44: residual view must be 16-byte aligned");
-    ConvKArgs K;
-    memset(&K, 0, sizeof(K));
-    K.Cin = Cin; K.Cout = Cout; K.T = 9; K.stride = 1;
-    K.N = io->N; K.H = io->H; K.W = io->W; K.Hout = io->H; K.Wout = io->W; K.Hfull = io->H; K.Wfull = io->W;
-    K.osy = K.osx = 1;
-    for (int i = 0; i < DCVIC_MAX_SRC; ++i) {
-        if (i < io->n_src) { K.src[i] = io->src[i].ptr; K.srcC[i] = io->src[i].C; K.src_bs[i] = io->src[i].batch_stride; }
-        else { K.src[i] = io->src[0].ptr; K.srcC[i] = 1 << 30; K.src_bs[i] = 0; }
-    }
-    K.out = io->out; K.out_bs = io->out_batch_stride; K.bias = io->bias; K.act = io->act;
-    K.res = io->res; K.res_bs = io->res_batch_stride;
-    K.wp = packed;
     K.gn_part = gn_part;
-    K.n_chunks = (Cin + F4_KC - 1) / F4_KC;
-    K.n_cotiles = (Cout + F4_CO - 1) / F4_CO;
-    K.tiles_y = (io->H + F4_TH - 1) / F4_TH;
-    K.tiles_x = (io->W + F4_TW - 1) / F4_TW;
-    const long long blocks = (long long)io->N * K.tiles_y * K.tiles_x * K.n_cotiles;
-    DCVIC_CHECK_ARG(blocks < (1ll << 31), "conv3x3_wino44: grid too large");
-    K.nblocks = (int)blocks;
+    if (const int rc = dcvic_conv_tiles("conv3x3_wino44", &K, F4_KC, F4_CO, F4_TH, F4_TW)) return rc;
     static std::atomic<unsigned> attr_mask{0};
     if (DcvicAttrOnce once_{attr_mask})
         hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wino44_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    // persistent grid: one workgroup per CU, a multiple of the 8 XCDs; each walks its share of the tiles
-    int grid = (dcvic_num_cu() / NXCD) * NXCD;
-    if (grid < NXCD) grid = NXCD;
-    if ((long long)grid > blocks) grid = (int)((blocks + NXCD - 1) / NXCD) * NXCD;
-    conv3x3_wino44_kernel<<<grid, F4_THREADS, F4_LDS_FLOATS * sizeof(float), (hipStream_t)stream>>>(K);
+    // persistent grid: each workgroup walks its share of the tiles
+    conv3x3_wino44_kernel<<<dcvic_persistent_grid(K.nblocks), F4_THREADS, F4_LDS_FLOATS * sizeof(float), (hipStream_t)stream>>>(K);
     DCVIC_CHECK_LAUNCH("conv3x3_wino44");
     return DCVIC_OK;
 }

@@ -40,6 +40,11 @@ def _bs(t: Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1] * t.shape[2] * t.shape[3])
 
 
+def _vec16(t: Tensor) -> bool:
+    """A 16-byte view: 16-byte aligned base and a batch stride of whole float4s (what the Winograd kernels load and store)."""
+    return t.data_ptr() % 16 == 0 and _bs(t) % 4 == 0
+
+
 def _p(t: Optional[Tensor]) -> C.c_void_p:
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
@@ -148,6 +153,9 @@ WINO44_MIN_BLOCKS = int(os.environ.get("DCVIC_WINO44_MIN_BLOCKS", "16"))   # wor
 WINO44_ENABLED = os.environ.get("DCVIC_WINO44", "1") != "0"   # F(4x4,3x3) for the layers that opted in (ConvPlan.wino44)
 WINO_MIN_BLOCKS = int(os.environ.get("DCVIC_WINO_MIN_BLOCKS", "16"))   # workgroups PER IMAGE below which the direct kernels run
 BF16_KERNEL_VARIANT = 9300        # conv3x3_bf16_kernel<false>; 9301 with the fused x2 upsample
+# ConvPlan routes with a weight pack of their own: route -> (C-ABI name stem of dcvic_<stem>_packed_bytes / dcvic_<stem>_pack_f32, dtype)
+_ROUTE_PACKS = {"bf16": ("conv3x3_bf16", torch.bfloat16), "wino44": ("wino44", torch.float32), "wino": ("wino", torch.float32),
+                "wino_ups": ("wino_ups", torch.float32)}
 
 
 class ConvPlan:
@@ -159,12 +167,8 @@ class ConvPlan:
 
     wino = False          # set by the owner: Winograd F(2x2,3x3) allowed (no integer decision downstream of this layer)
     wino44 = False        # set by the owner: F(4x4,3x3) allowed too -- post-argmax layers only (3x the F(2x2) rounding error)
-    _wino_pack = None
-    _wino44_pack = None
     last_gn_part = None   # (partial statistics [N, Cout, n_pt, 2], n_pt) written by the last call when gn_stats was asked AND the F(4x4) kernel ran
-    _wino_ups_pack = None
     bf16 = False          # set by the owner: bf16-MFMA kernel (csrc/conv_bf16.hip) when eligible -- decoder precision "bf16" only
-    _bf16_pack = None
     last_bf16 = False     # whether the last call ran on the bf16 kernel
     bf16_launches = 0     # calls that ran on the bf16 kernel / on the fp32 kernels (coverage record)
     fp32_launches = 0
@@ -182,25 +186,22 @@ class ConvPlan:
         self._w = w
         self.phases: List[list] = []      # [desc, {tile class: packed weights}, py, px]
         self.ups_phases = False
+        self._packs = {}                  # {route: packed weights} of the 3x3 fast paths, filled on first use (_packed)
         if kind == "conv" and upsample and tuple(w.shape[2:]) == (3, 3) and pad == (1, 1) and stride == 1 \
                 and os.environ.get("DCVIC_UPS_PHASES", "1") != "0":
             # nearest-x2 + conv3x3 == four 2x2 sub-pixel convolutions on the low-res input (4/9 of the flops):
             # output row 2m+py reads low-res rows {m-1, m} (py=0) or {m, m+1} (py=1) with the taps that land on
             # the same low-res row pre-added.  Zero padding is preserved (row -1 / row H are out of the image).
             self.Cout, self.Cin, self.KH, self.KW = w.shape
-            self.ups_phases = True
-            self._wphase = []
+            weffs = []
             for py in (0, 1):
                 rows = [w[:, :, 0], w[:, :, 1] + w[:, :, 2]] if py == 0 else [w[:, :, 0] + w[:, :, 1], w[:, :, 2]]
                 for px in (0, 1):
                     cols = []
                     for r in rows:       # r: [Cout, Cin, 3]
                         cols.append(torch.stack([r[:, :, 0], r[:, :, 1] + r[:, :, 2]] if px == 0 else [r[:, :, 0] + r[:, :, 1], r[:, :, 2]], dim=-1))
-                    weff = torch.stack(cols, dim=2).contiguous()    # [Cout, Cin, 2, 2]
-                    d = ConvDesc()
-                    check(lib().dcvic_conv_desc_init(C.byref(d), self.Cin, self.Cout, 2, 2, 1, 1 - py, 1 - px, 0), "conv_desc_init")
-                    self.phases.append([d, {}, py, px])
-                    self._wphase.append(weff)
+                    weffs.append(torch.stack(cols, dim=2))    # [Cout, Cin, 2, 2]
+            self._subpixel_phases(weffs)
         elif kind == "conv":
             self.Cout, self.Cin, self.KH, self.KW = w.shape
             d = ConvDesc()
@@ -234,50 +235,48 @@ class ConvPlan:
         self.bias = None
         self._w = None
         self.Cout, self.Cin, self.KH, self.KW = w0.shape[0], w0.shape[1], 3, 3
+        self.phases, self._packs = [], {}
+        self._subpixel_phases(wphases)
+        return self
+
+    def _subpixel_phases(self, weffs: Sequence[Tensor]) -> None:
+        """Direct-kernel phases of a x2 output from four 2x2 weights [Cout, Cin, 2, 2] in the order (0,0), (0,1), (1,0), (1,1)."""
         self.ups_phases = True
-        self.phases, self._wphase = [], []
-        for (py, px), wp in zip(((0, 0), (0, 1), (1, 0), (1, 1)), wphases):
+        self._wphase = []
+        for (py, px), wp in zip(((0, 0), (0, 1), (1, 0), (1, 1)), weffs):
             d = ConvDesc()
             check(lib().dcvic_conv_desc_init(C.byref(d), self.Cin, self.Cout, 2, 2, 1, 1 - py, 1 - px, 0), "conv_desc_init")
             self.phases.append([d, {}, py, px])
             self._wphase.append(wp.detach().contiguous())
-        return self
+
+    def _is_3x3(self) -> bool:
+        """Conv2d(k3, s1, p1) with its own weights, without the upsample."""
+        return self.kind == "conv" and not self.upsample and not self.ups_phases and self.stride == 1 and self.pad == (1, 1) \
+            and (self.KH, self.KW) == (3, 3) and self._w is not None
+
+    def _wino_fills(self, srcs, H: int, W: int, Ho: int, Wo: int, th: int, min_blocks: int) -> bool:
+        """Winograd eligibility shared by the three forms: input width % 4 == 0, at least 48 output channels, every source a 16-byte view
+        of a multiple of 8 channels, and an Ho x Wo output that fills its 64-channel x th x 32-pixel workgroup tiles, at least min_blocks
+        of them per image.  A function of the LAYER and the IMAGE size only, never of N: a reconstruction must not depend on the batch it
+        was decoded in."""
+        if (W & 3) or self.Cout < 48 or any(s.shape[1] % 8 or not _vec16(s) for s in srcs):
+            return False
+        ty, tx = (Ho + th - 1) // th, (Wo + 31) // 32
+        if Ho * Wo < 0.6 * (ty * th * tx * 32):
+            return False
+        return ty * tx * ((self.Cout + 63) // 64) >= min_blocks
 
     def _wino_ok(self, srcs, N: int, H: int, W: int) -> bool:
-        """Winograd eligibility: Conv2d(k3, s1, p1), 8-channel-aligned sources, even width, and a map that fills its
-        64-channel x 8 x 32-pixel workgroup tiles.  A function of the LAYER and the IMAGE size only, never of N: a
-        reconstruction must not depend on the batch it was decoded in."""
-        if self.kind != "conv" or self.upsample or self.ups_phases or self.stride != 1 or self.pad != (1, 1) \
-                or (self.KH, self.KW) != (3, 3) or self._w is None:
-            return False
-        if (W & 3) or self.Cout < 48 or any(s.shape[1] % 8 or s.data_ptr() % 16 or (s.shape[0] > 1 and s.stride(0) % 4) for s in srcs):
-            return False
-        ty, tx = (H + 7) // 8, (W + 31) // 32
-        if H * W < 0.6 * (ty * 8 * tx * 32):
-            return False
-        return ty * tx * ((self.Cout + 63) // 64) >= WINO_MIN_BLOCKS
+        """F(2x2, 3x3) eligibility: Conv2d(k3, s1, p1) on 8 x 32-pixel tiles (_wino_fills)."""
+        return self._is_3x3() and self._wino_fills(srcs, H, W, H, W, 8, WINO_MIN_BLOCKS)
 
     def _wino44_ok(self, srcs, N: int, H: int, W: int) -> bool:
-        """F(4x4, 3x3) eligibility: Conv2d(k3, s1, p1), every source a multiple of 8 channels, width % 4 == 0, and a map that fills its
-        64-channel x 16 x 32-pixel workgroup tiles.  A function of the layer and the image size only, never of N."""
-        if self.kind != "conv" or self.upsample or self.ups_phases or self.stride != 1 or self.pad != (1, 1) \
-                or (self.KH, self.KW) != (3, 3) or self._w is None:
-            return False
-        if (W & 3) or self.Cout < 48 or any(s.shape[1] % 8 or s.data_ptr() % 16 or (s.shape[0] > 1 and s.stride(0) % 4) for s in srcs):
-            return False
-        ty, tx = (H + 15) // 16, (W + 31) // 32
-        if H * W < 0.6 * (ty * 16 * tx * 32):
-            return False
-        return ty * tx * ((self.Cout + 63) // 64) >= WINO44_MIN_BLOCKS
+        """F(4x4, 3x3) eligibility: Conv2d(k3, s1, p1) on 16 x 32-pixel tiles (_wino_fills)."""
+        return self._is_3x3() and self._wino_fills(srcs, H, W, H, W, 16, WINO44_MIN_BLOCKS)
 
     def _wino_ups_ok(self, srcs, H: int, W: int) -> bool:
         """Eligibility of the upsample-fused Winograd (input H x W, output 2H x 2W): as _wino_ok, on the output's tile grid."""
-        if (W & 3) or self.Cout < 48 or any(s.shape[1] % 8 or s.data_ptr() % 16 or (s.shape[0] > 1 and s.stride(0) % 4) for s in srcs):
-            return False
-        ty, tx = (2 * H + 7) // 8, (2 * W + 31) // 32
-        if 4 * H * W < 0.6 * (ty * 8 * tx * 32):
-            return False
-        return ty * tx * ((self.Cout + 63) // 64) >= WINO_MIN_BLOCKS
+        return self._wino_fills(srcs, H, W, 2 * H, 2 * W, 8, WINO_MIN_BLOCKS)
 
     def _bf16_ok(self, srcs, out_hw) -> bool:
         """bf16-kernel eligibility: Conv2d(k3, s1, p1), optionally behind the nearest x2 upsample, every source a multiple of 8 channels,
@@ -361,142 +360,110 @@ class ConvPlan:
             if sc.shape[0] not in (1, N):
                 raise ValueError("conv affine batch must be 1 or N")
         st = _stream()
-        if self.bf16 and init is None and self._bf16_ok(srcs, out_hw):
-            if self._bf16_pack is None:       # owned by the plan: a weight change builds a new plan (layers._Packed key) and re-packs
-                nbytes = lib().dcvic_conv3x3_bf16_packed_bytes(self.Cin, self.Cout)
-                self._bf16_pack = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=self._w.device)
-                check(lib().dcvic_conv3x3_bf16_pack_f32(_p(self._w), _p(self._bf16_pack), self.Cin, self.Cout, st), "conv3x3_bf16_pack")
-            io.Hout, io.Wout = Hf, Wf
-            io.osy = io.osx = 1
-            io.ooy = io.oox = 0
-            ups = 1 if self.upsample else 0
+        route = self._route(srcs, out, act, res, affine, out_hw, init, N, H, W)
+        if route == "bf16":
             self.last_bf16 = True
             self.bf16_launches += 1
-            if _EVENTS is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                check(lib().dcvic_conv3x3_bf16_f32(self.Cin, self.Cout, ups, _p(self._bf16_pack), C.byref(io), st), "conv3x3_bf16")
-                e1.record()
-                _EVENTS.append((BF16_KERNEL_VARIANT + ups, 2.0 * N * Hf * Wf * self.Cout * self.Cin * 9, e0, e1, (self.Cin, self.Cout, 9, 1, ups, H, W, N)))
-            else:
-                check(lib().dcvic_conv3x3_bf16_f32(self.Cin, self.Cout, ups, _p(self._bf16_pack), C.byref(io), st), "conv3x3_bf16")
-            return out
-        self.fp32_launches += 1
-        if THIN_ENABLED and self.kind == "conv" and not self.upsample and not self.ups_phases and self.stride == 1 and self.pad == (1, 1) \
-                and (self.KH, self.KW) == (3, 3) and self._w is not None and len(srcs) == 1 and init is None and affine is None \
-                and (out_hw is None or tuple(out_hw) == (H, W)) and H * W >= THIN_MIN_PIXELS \
-                and lib().dcvic_conv3x3_thin_applies(self.Cin, self.Cout):
+        else:
+            self.fp32_launches += 1
+        if route != "direct":
+            io.Hout, io.Wout = Hf, Wf
+            io.osy = io.osx = 1
+            io.ooy = io.oox = 0
+        L = lib()
+        if route == "bf16":
+            ups = 1 if self.upsample else 0
+            self._launch("conv3x3_bf16", L.dcvic_conv3x3_bf16_f32, (self.Cin, self.Cout, ups, _p(self._packed("bf16")), C.byref(io), st),
+                         BF16_KERNEL_VARIANT + ups, N, H, W, Hf, Wf, ups=ups)
+        elif route == "thin":
             # a thin layer (VQGAN conv_in 3 -> 128, conv_out 128 -> 3): HBM-bound VALU kernel, bit-identical to the MFMA kernels' order
-            io.Hout, io.Wout = Hf, Wf
-            io.osy = io.osx = 1
-            io.ooy = io.oox = 0
             var = 9200 + self.Cout if self.Cout <= 4 and self.Cin >= 8 else 9210 + self.Cin
-            if _EVENTS is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                check(lib().dcvic_conv3x3_thin_f32(_p(self._w), self.Cin, self.Cout, C.byref(io), st), "conv3x3_thin")
-                e1.record()
-                _EVENTS.append((var, 2.0 * N * H * W * self.Cout * self.Cin * 9, e0, e1, (self.Cin, self.Cout, 9, 1, 0, H, W, N)))
-            else:
-                check(lib().dcvic_conv3x3_thin_f32(_p(self._w), self.Cin, self.Cout, C.byref(io), st), "conv3x3_thin")
-            return out
-        if self.wino44 and WINO44_ENABLED and self.wino and WINO_ENABLED and not self.ups_phases and not self.upsample and init is None and affine is None \
-                and act in (ACT_NONE, ACT_RELU, ACT_LRELU02) \
-                and (self.wino44 == "force" or self._wino44_ok(srcs, N, H, W)) \
-                and out.data_ptr() % 16 == 0 and _bs(out) % 4 == 0 and (res is None or (res.data_ptr() % 16 == 0 and _bs(res) % 4 == 0)):
-            if self._wino44_pack is None:
-                nbytes = lib().dcvic_wino44_packed_bytes(self.Cin, self.Cout)
-                self._wino44_pack = torch.empty(nbytes // 4, dtype=torch.float32, device=self._w.device)
-                check(lib().dcvic_wino44_pack_f32(_p(self._w), _p(self._wino44_pack), self.Cin, self.Cout, st), "wino44_pack")
-            io.Hout, io.Wout = Hf, Wf
-            io.osy = io.osx = 1
-            io.ooy = io.oox = 0
-            part = None
+            self._launch("conv3x3_thin", L.dcvic_conv3x3_thin_f32, (_p(self._w), self.Cin, self.Cout, C.byref(io), st), var, N, H, W, H, W)
+        elif route == "wino44":
+            packed = _p(self._packed("wino44"))
             if gn_stats and GN_FUSED_STATS:
-                n_pt = int(lib().dcvic_wino44_stats_tiles(H, W))
+                n_pt = int(L.dcvic_wino44_stats_tiles(H, W))
                 part = torch.empty((N, self.Cout, n_pt, 2), dtype=torch.float32, device=out.device)
                 self.last_gn_part = (part, n_pt)
-
-            def launch():
-                if part is None:
-                    check(lib().dcvic_conv3x3_wino44_f32(self.Cin, self.Cout, _p(self._wino44_pack), C.byref(io), st), "conv3x3_wino44")
-                else:
-                    check(lib().dcvic_conv3x3_wino44_stats_f32(self.Cin, self.Cout, _p(self._wino44_pack), C.byref(io), _p(part), st), "conv3x3_wino44_stats")
-            if _EVENTS is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                launch()
-                e1.record()
-                _EVENTS.append((9104, 2.0 * N * H * W * self.Cout * self.Cin * 9, e0, e1, (self.Cin, self.Cout, 9, 1, 0, H, W, N)))
+                self._launch("conv3x3_wino44_stats", L.dcvic_conv3x3_wino44_stats_f32, (self.Cin, self.Cout, packed, C.byref(io), _p(part), st),
+                             9104, N, H, W, H, W)
             else:
-                launch()
-            return out
-        if self.wino and WINO_ENABLED and not self.ups_phases and not self.upsample and init is None and affine is None \
-                and (self.wino == "force" or self._wino_ok(srcs, N, H, W)) \
-                and out.data_ptr() % 16 == 0 and _bs(out) % 4 == 0 and (res is None or (res.data_ptr() % 16 == 0 and _bs(res) % 4 == 0)):
-            if self._wino_pack is None:
-                nbytes = lib().dcvic_wino_packed_bytes(self.Cin, self.Cout)
-                self._wino_pack = torch.empty(nbytes // 4, dtype=torch.float32, device=self._w.device)
-                check(lib().dcvic_wino_pack_f32(_p(self._w), _p(self._wino_pack), self.Cin, self.Cout, st), "wino_pack")
-            io.Hout, io.Wout = Hf, Wf
-            io.osy = io.osx = 1
-            io.ooy = io.oox = 0
-            if _EVENTS is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                check(lib().dcvic_conv3x3_wino_f32(self.Cin, self.Cout, _p(self._wino_pack), C.byref(io), st), "conv3x3_wino")
-                e1.record()
-                _EVENTS.append((9100, 2.0 * N * H * W * self.Cout * self.Cin * 9, e0, e1, (self.Cin, self.Cout, 9, 1, 0, H, W, N)))
-            else:
-                check(lib().dcvic_conv3x3_wino_f32(self.Cin, self.Cout, _p(self._wino_pack), C.byref(io), st), "conv3x3_wino")
-            return out
-        if self.wino and WINO_ENABLED and self.ups_phases and self._w is not None and init is None and affine is None \
-                and (self.wino == "force" or self._wino_ups_ok(srcs, H, W)) \
-                and out.data_ptr() % 16 == 0 and _bs(out) % 4 == 0 and (res is None or (res.data_ptr() % 16 == 0 and _bs(res) % 4 == 0)):
+                self._launch("conv3x3_wino44", L.dcvic_conv3x3_wino44_f32, (self.Cin, self.Cout, packed, C.byref(io), st), 9104, N, H, W, H, W)
+        elif route == "wino":
+            self._launch("conv3x3_wino", L.dcvic_conv3x3_wino_f32, (self.Cin, self.Cout, _p(self._packed("wino")), C.byref(io), st),
+                         9100, N, H, W, H, W)
+        elif route == "wino_ups":
             # nearest x2 + conv3x3 as the 9-position structured Winograd (csrc/wino.hip) instead of four 2x2 phase convolutions
-            if self._wino_ups_pack is None:
-                nbytes = lib().dcvic_wino_ups_packed_bytes(self.Cin, self.Cout)
-                self._wino_ups_pack = torch.empty(nbytes // 4, dtype=torch.float32, device=self._w.device)
-                check(lib().dcvic_wino_ups_pack_f32(_p(self._w), _p(self._wino_ups_pack), self.Cin, self.Cout, st), "wino_ups_pack")
-            io.Hout, io.Wout = Hf, Wf
-            io.osy = io.osx = 1
-            io.ooy = io.oox = 0
-            if _EVENTS is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                check(lib().dcvic_conv3x3_wino_ups_f32(self.Cin, self.Cout, _p(self._wino_ups_pack), C.byref(io), st), "conv3x3_wino_ups")
-                e1.record()
-                _EVENTS.append((9101, 2.0 * N * Hf * Wf * self.Cout * self.Cin * 9, e0, e1, (self.Cin, self.Cout, 9, 1, 1, H, W, N)))
-            else:
-                check(lib().dcvic_conv3x3_wino_ups_f32(self.Cin, self.Cout, _p(self._wino_ups_pack), C.byref(io), st), "conv3x3_wino_ups")
-            return out
-        for phi, ph in enumerate(self.phases):
-            d, packs, py, px = ph
-            if self.ups_phases or (self.kind == "convT" and self.KH == 5):
-                io.Hout, io.Wout = H, W
-                io.osy = io.osx = 2
-                io.ooy, io.oox = py, px
-            else:
-                io.Hout, io.Wout = Hf, Wf
-                io.osy = io.osx = 1
-                io.ooy = io.oox = 0
-            cls = lib().dcvic_conv_select_class(C.byref(d), N, io.Hout, io.Wout)
-            if cls < 0:
-                check(cls, "conv_select_class")
-            d.cfg = cls
-            packed = packs.get(cls)
-            if packed is None:
-                packed = packs[cls] = self._pack(d, self._wphase[phi] if self.ups_phases else self._w)
-            if _EVENTS is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                check(lib().dcvic_conv2d_f32(C.byref(d), _p(packed), C.byref(io), st), "conv2d")
-                e1.record()
-                _EVENTS.append((int(lib().dcvic_conv_last_variant()), 2.0 * N * io.Hout * io.Wout * self.Cout * self.Cin * int(d.T), e0, e1,
-                                (self.Cin, self.Cout, int(d.T), self.stride, int(self.upsample), H, W, N)))
-            else:
-                check(lib().dcvic_conv2d_f32(C.byref(d), _p(packed), C.byref(io), st), "conv2d")
+            self._launch("conv3x3_wino_ups", L.dcvic_conv3x3_wino_ups_f32, (self.Cin, self.Cout, _p(self._packed("wino_ups")), C.byref(io), st),
+                         9101, N, H, W, Hf, Wf, ups=1)
+        else:
+            for phi, (d, packs, py, px) in enumerate(self.phases):
+                if self.ups_phases or (self.kind == "convT" and self.KH == 5):
+                    io.Hout, io.Wout = H, W
+                    io.osy = io.osx = 2
+                    io.ooy, io.oox = py, px
+                else:
+                    io.Hout, io.Wout = Hf, Wf
+                    io.osy = io.osx = 1
+                    io.ooy = io.oox = 0
+                cls = L.dcvic_conv_select_class(C.byref(d), N, io.Hout, io.Wout)
+                if cls < 0:
+                    check(cls, "conv_select_class")
+                d.cfg = cls
+                packed = packs.get(cls)
+                if packed is None:
+                    packed = packs[cls] = self._pack(d, self._wphase[phi] if self.ups_phases else self._w)
+                self._launch("conv2d", L.dcvic_conv2d_f32, (C.byref(d), _p(packed), C.byref(io), st), None, N, H, W, io.Hout, io.Wout,
+                             T=int(d.T), stride=self.stride, ups=int(self.upsample))
         return out
+
+    def _route(self, srcs, out, act, res, affine, out_hw, init, N: int, H: int, W: int) -> str:
+        """The kernel family of one call, first match in this order: "bf16", "thin", "wino44" (F(4x4)), "wino" (F(2x2)), "wino_ups"
+        (F(2x2) behind the x2 upsample), else "direct" (dcvic_conv2d_f32 per phase).  A "force" in .wino / .wino44 skips the tile-fill
+        test of that form only."""
+        if self.bf16 and init is None and self._bf16_ok(srcs, out_hw):
+            return "bf16"
+        if THIN_ENABLED and self._is_3x3() and len(srcs) == 1 and init is None and affine is None \
+                and (out_hw is None or tuple(out_hw) == (H, W)) and H * W >= THIN_MIN_PIXELS \
+                and lib().dcvic_conv3x3_thin_applies(self.Cin, self.Cout):
+            return "thin"
+        if not (self.wino and WINO_ENABLED and init is None and affine is None and _vec16(out) and (res is None or _vec16(res))):
+            return "direct"
+        if not self.ups_phases and not self.upsample:
+            if self.wino44 and WINO44_ENABLED and act in (ACT_NONE, ACT_RELU, ACT_LRELU02) \
+                    and (self.wino44 == "force" or self._wino44_ok(srcs, N, H, W)):
+                return "wino44"
+            if self.wino == "force" or self._wino_ok(srcs, N, H, W):
+                return "wino"
+        elif self.ups_phases and self._w is not None and (self.wino == "force" or self._wino_ups_ok(srcs, H, W)):
+            return "wino_ups"
+        return "direct"
+
+    def _packed(self, route: str) -> Tensor:
+        """The weights packed for `route`, built on first use.  Owned by the plan: a weight change builds a new plan (layers._Packed key)
+        and re-packs."""
+        packed = self._packs.get(route)
+        if packed is None:
+            stem, dtype = _ROUTE_PACKS[route]
+            L = lib()
+            nbytes = getattr(L, f"dcvic_{stem}_packed_bytes")(self.Cin, self.Cout)
+            packed = self._packs[route] = torch.empty(nbytes // dtype.itemsize, dtype=dtype, device=self._w.device)
+            check(getattr(L, f"dcvic_{stem}_pack_f32")(_p(self._w), _p(packed), self.Cin, self.Cout, _stream()), f"{stem}_pack")
+        return packed
+
+    def _launch(self, what: str, fn, args, variant: Optional[int], N: int, H: int, W: int, Ho: int, Wo: int,
+                T: int = 9, stride: int = 1, ups: int = 0) -> None:
+        """check(fn(*args)); under kernel_events_start() also time it and record (variant, flops, e0, e1, shape).  variant None: the
+        one dcvic_conv2d_f32 reports."""
+        if _EVENTS is None:
+            check(fn(*args), what)
+            return
+        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        check(fn(*args), what)
+        e1.record()
+        _EVENTS.append((int(lib().dcvic_conv_last_variant()) if variant is None else variant, 2.0 * N * Ho * Wo * self.Cout * self.Cin * T,
+                        e0, e1, (self.Cin, self.Cout, T, stride, ups, H, W, N)))
 
 
 # ------------------------------------------------------------------------------------------- gemm

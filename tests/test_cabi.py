@@ -60,7 +60,7 @@ def test_wino_packed_bytes_host_formula():
 # after the child has confirmed that HIP sees no device.  The buffers are dummy non-null addresses: the checks must reject the
 # arguments before any launch, and if a check ever stopped doing so the launch would fail for want of a device instead of touching
 # memory that does not exist.
-_ARG_CHECKS = r"""
+_NO_GPU_PRELUDE = r"""
 import ctypes as C, sys
 sys.path.insert(0, sys.argv[1])
 from dc_vic_amd import _lib
@@ -78,7 +78,20 @@ def err(rc, *words):
     msg = L.dcvic_last_error().decode()
     for w in words:
         assert w in msg, msg
+"""
 
+
+def _run_without_gpu(script: str) -> None:
+    """Runs _NO_GPU_PRELUDE + script in a child process with every GPU hidden; the script prints CHECKS_OK at its end."""
+    import subprocess
+    import sys
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", _NO_GPU_PRELUDE + script, ROOT], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 3, "HIP still sees a device with every device hidden: the checks were not run"
+    assert r.returncode == 0 and "CHECKS_OK" in r.stdout, r.stdout + r.stderr
+
+
+_ARG_CHECKS = r"""
 # copy_planes(dst, dst_bs, dstH, dstW, src, src_bs, srcH, srcW, N, C, copyH, copyW, reflect, stream): src 6x5, dst 12x10
 cp = lambda copyH, copyW, reflect: L.dcvic_copy_planes_f32(P, LL(3 * 120), 12, 10, P, LL(3 * 30), 6, 5, 2, 3, copyH, copyW, reflect, None)
 err(cp(12, 5, 1), "copy_planes", "reflect")        # a reflection by H (torch 'reflect' needs pad < H)
@@ -105,18 +118,176 @@ err(L.dcvic_neglog2_sum_f32(P, LL(10), P, P, 1025, LL(10), None), "neglog2_sum")
 err(L.dcvic_neglog2_sum_f32(P, LL(9), P, P, 2, LL(10), None), "neglog2_sum")
 assert L.dcvic_rate_blocks(LL(1)) == 1 and L.dcvic_rate_blocks(LL(2048)) == 1 and L.dcvic_rate_blocks(LL(2049)) == 2
 assert L.dcvic_rate_blocks(LL(64 * 2048)) == 64 and L.dcvic_rate_blocks(LL(10 ** 9)) == 64
-print("ARG_CHECKS_OK")
+print("CHECKS_OK")
 """
 
 
 def test_rate_and_copy_argument_checks_without_gpu():
     """The rate and copy entry points reject bad arguments in their host-side checks, before any launch (see _ARG_CHECKS)."""
-    import subprocess
-    import sys
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
-    r = subprocess.run([sys.executable, "-c", _ARG_CHECKS, ROOT], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode != 3, "HIP still sees a device with every device hidden: the checks were not run"
-    assert r.returncode == 0 and "ARG_CHECKS_OK" in r.stdout, r.stdout + r.stderr
+    _run_without_gpu(_ARG_CHECKS)
+
+
+# Every case breaks exactly one rule of one convolution entry point and keeps every other argument valid, so the order in which an
+# entry point runs its checks does not matter.  Baseline layer: N = 2, one 16-channel 8 x 8 source, 16 output channels (3 for thin).
+_CONV_ARG_CHECKS = r"""
+N, CIN, H, W = 2, 16, 8, 8
+
+def make_io(cout=16, up=False, srcs=(CIN,), h=H, w=W):
+    io = _lib.ConvIO()
+    io.N, io.H, io.W = N, h, w
+    ho, wo = (2 * h, 2 * w) if up else (h, w)
+    io.Hout, io.Wout, io.Hfull, io.Wfull = ho, wo, ho, wo
+    io.osy = io.osx = 1
+    io.n_src = len(srcs)
+    for i, c in enumerate(srcs):
+        io.src[i].ptr = 64; io.src[i].C = c; io.src[i].batch_stride = c * h * w
+    io.out = 64; io.out_batch_stride = cout * ho * wo
+    io.act = 0
+    return io
+
+def variant(io, **kw):
+    io = type(io).from_buffer_copy(io)
+    for k, v in kw.items():
+        if k.startswith("src0_"):
+            setattr(io.src[0], k[5:], v)
+        else:
+            setattr(io, k, v)
+    return io
+
+def with_res(io, cout, **kw):
+    return variant(io, **{"res": 64, "res_batch_stride": cout * io.Hfull * io.Wfull, **kw})
+
+d = _lib.ConvDesc()
+assert L.dcvic_conv_desc_init(C.byref(d), CIN, 16, 3, 3, 1, 1, 1, 0) == 0
+def conv2d(io, packed=P, desc=d):
+    return L.dcvic_conv2d_f32(C.byref(desc), packed, None if io is None else C.byref(io), None)
+def wino(io, packed=P, cin=CIN):
+    return L.dcvic_conv3x3_wino_f32(cin, 16, packed, None if io is None else C.byref(io), None)
+def wino_ups(io, packed=P, cin=CIN):
+    return L.dcvic_conv3x3_wino_ups_f32(cin, 16, packed, None if io is None else C.byref(io), None)
+def wino44(io, packed=P, cin=CIN):
+    return L.dcvic_conv3x3_wino44_f32(cin, 16, packed, None if io is None else C.byref(io), None)
+def wino44_stats(io, packed=P, cin=CIN, part=P):
+    return L.dcvic_conv3x3_wino44_stats_f32(cin, 16, packed, None if io is None else C.byref(io), part, None)
+def bf16(io, packed=P, cin=CIN, up=0):
+    return L.dcvic_conv3x3_bf16_f32(cin, 16, up, packed, None if io is None else C.byref(io), None)
+def thin(io, packed=P, cin=CIN, cout=3):
+    return L.dcvic_conv3x3_thin_f32(packed, cin, cout, None if io is None else C.byref(io), None)
+
+# (entry point, error prefixes its messages may start with, the call, its output channels, whether it maps H x W to 2H x 2W)
+ENTRIES = [
+    ("conv2d", ("conv2d",), conv2d, 16, False),
+    ("wino", ("conv3x3_wino",), wino, 16, False),
+    ("wino_ups", ("conv3x3_wino_ups",), wino_ups, 16, True),
+    ("wino44", ("conv3x3_wino44",), wino44, 16, False),
+    ("wino44_stats", ("conv3x3_wino44", "conv3x3_wino44_stats"), wino44_stats, 16, False),
+    ("bf16", ("conv3x3_bf16",), bf16, 16, False),
+    ("thin", ("conv3x3_thin",), thin, 3, False),
+]
+n_cases = 0
+
+def rejects(prefixes, rc, what):
+    global n_cases
+    assert rc == -1, (what, rc)
+    msg = L.dcvic_last_error().decode()
+    assert msg.split(":")[0] in prefixes, (what, msg)
+    n_cases += 1
+
+for name, prefixes, call, cout, up in ENTRIES:
+    io = make_io(cout, up)
+    hw = io.Hfull * io.Wfull
+    def rej(rc, what):
+        rejects(prefixes, rc, f"{name}: {what}")
+    rej(call(None), "null io")
+    rej(call(variant(io, out=None)), "null out")
+    rej(call(io, packed=None), "null packed weights")
+    rej(call(variant(io, n_src=0)), "n_src 0")
+    rej(call(variant(io, n_src=4)), "n_src 4")
+    rej(call(variant(io, src0_C=8)), "channel sum below Cin")
+    rej(call(make_io(cout, up, srcs=(8, 16))), "channel sum above Cin")
+    rej(call(variant(io, src0_batch_stride=CIN * H * W - 4)), "source batch stride")
+    rej(call(variant(io, out_batch_stride=cout * hw - 4)), "output batch stride")
+    rej(call(with_res(io, cout, res_batch_stride=cout * hw - 4)), "residual batch stride")
+
+# Winograd x3 and bf16: 8-channel sources
+rejects(("conv3x3_wino",), wino(make_io(srcs=(12,)), cin=12), "wino: 12 channels")
+rejects(("conv3x3_wino_ups",), wino_ups(make_io(up=True, srcs=(12,)), cin=12), "wino_ups: 12 channels")
+rejects(("conv3x3_wino44",), wino44(make_io(srcs=(12,)), cin=12), "wino44: 12 channels")
+rejects(("conv3x3_wino44", "conv3x3_wino44_stats"), wino44_stats(make_io(srcs=(12,)), cin=12), "wino44_stats: 12 channels")
+rejects(("conv3x3_bf16",), bf16(make_io(srcs=(12,)), cin=12), "bf16: 12 channels")
+
+# Winograd x3: 16-byte views, W % 4, no affine / init, geometry
+for name, prefixes, call, cout, up in ENTRIES[1:5]:
+    io = make_io(16, up)
+    hw = io.Hfull * io.Wfull
+    def rej(rc, what):
+        rejects(prefixes, rc, f"{name}: {what}")
+    rej(call(variant(io, src0_ptr=68)), "misaligned source")
+    rej(call(variant(io, out=68)), "misaligned output")
+    rej(call(with_res(io, 16, res=68)), "misaligned residual")
+    rej(call(variant(io, src0_batch_stride=CIN * H * W + 2)), "source batch stride % 4")
+    rej(call(variant(io, out_batch_stride=16 * hw + 2)), "output batch stride % 4")
+    rej(call(with_res(io, 16, res_batch_stride=16 * hw + 2)), "residual batch stride % 4")
+    rej(call(make_io(16, up, w=6)), "W % 4")
+    rej(call(variant(io, aff_scale=64, aff_shift=64)), "affine")
+    rej(call(variant(io, aff_scale=64)), "affine scale only")
+    rej(call(variant(io, init=64, init_batch_stride=16 * hw)), "init")
+    other = make_io(16, not up)
+    rej(call(variant(other, out_batch_stride=16 * 4 * H * W)), "output geometry")
+    rej(call(variant(io, Hout=io.Hout - 1)), "Hout")
+    rej(call(variant(io, Wfull=io.Wfull + 4, out_batch_stride=16 * io.Hfull * (io.Wfull + 4))), "Wfull")
+    rej(call(variant(io, osy=2)), "scatter")
+    rej(call(variant(io, oox=1)), "offset")
+
+# wino44: activation set, statistics buffer
+io = make_io()
+rejects(("conv3x3_wino44",), wino44(variant(io, act=3)), "wino44: ACT_SWISH")
+rejects(("conv3x3_wino44", "conv3x3_wino44_stats"), wino44_stats(variant(io, act=3)), "wino44_stats: ACT_SWISH")
+rejects(("conv3x3_wino44", "conv3x3_wino44_stats"), wino44_stats(io, part=None), "wino44_stats: null gn_part")
+
+# bf16: no init, two-sided affine, output H x W (2H x 2W when upsampling)
+pb = ("conv3x3_bf16",)
+rejects(pb, bf16(variant(io, init=64, init_batch_stride=16 * H * W)), "bf16: init")
+rejects(pb, bf16(variant(io, aff_scale=64)), "bf16: affine scale only")
+rejects(pb, bf16(variant(io, aff_shift=64)), "bf16: affine shift only")
+rejects(pb, bf16(variant(io, Hout=12, Hfull=12, out_batch_stride=16 * 12 * W)), "bf16: output 12 x 8")
+rejects(pb, bf16(variant(make_io(up=True), Wout=W, Wfull=W, out_batch_stride=16 * 2 * H * W)), "bf16: output 16 x 8")
+rejects(pb, bf16(io, up=1), "bf16: upsample onto an H x W output")
+rejects(pb, bf16(make_io(up=True), up=0), "bf16: 2H x 2W output without upsample")
+rejects(pb, bf16(variant(io, osx=2)), "bf16: scatter")
+
+# thin: one source, a thin layer, no affine / init
+pt = ("conv3x3_thin",)
+io = make_io(3)
+rejects(pt, thin(make_io(3, srcs=(8, 8))), "thin: two sources")
+rejects(pt, thin(make_io(16), cout=16), "thin: 16 -> 16")
+rejects(pt, thin(make_io(3, srcs=(12,)), cin=12), "thin: 12 -> 3")
+rejects(pt, thin(variant(io, aff_scale=64, aff_shift=64)), "thin: affine")
+rejects(pt, thin(variant(io, init=64, init_batch_stride=3 * H * W)), "thin: init")
+rejects(pt, thin(variant(io, Wout=W - 1)), "thin: geometry")
+
+# conv2d: scatter inside Hfull x Wfull, cfg 0..3, two-sided affine, planes below 2^30
+p2 = ("conv2d",)
+io = make_io()
+rejects(p2, conv2d(variant(io, ooy=1)), "conv2d: scatter past Hfull")
+rejects(p2, conv2d(variant(io, osx=2, Wout=5)), "conv2d: scatter past Wfull")
+rejects(p2, conv2d(variant(io, init=64, init_batch_stride=16 * H * W - 4)), "conv2d: init batch stride")
+for cfg in (-1, 4):
+    dc = _lib.ConvDesc.from_buffer_copy(d); dc.cfg = cfg
+    rejects(p2, conv2d(io, desc=dc), f"conv2d: cfg {cfg}")
+rejects(p2, conv2d(variant(io, aff_scale=64)), "conv2d: affine scale only")
+rejects(p2, conv2d(variant(io, aff_shift=64)), "conv2d: affine shift only")
+big = make_io(h=1 << 15, w=1 << 15)
+rejects(p2, conv2d(big), "conv2d: input plane 2^30")
+rejects(p2, conv2d(variant(io, Hfull=1 << 15, Wfull=1 << 15, out_batch_stride=16 << 30)), "conv2d: output plane 2^30")
+assert n_cases == 7 * 10 + 5 + 4 * 15 + 3 + 8 + 6 + 9, n_cases
+print("CHECKS_OK")
+"""
+
+
+def test_conv_argument_checks_without_gpu():
+    """The seven convolution entry points reject what their contracts exclude, before any launch (see _CONV_ARG_CHECKS)."""
+    _run_without_gpu(_CONV_ARG_CHECKS)
 
 
 def test_copy_window_shape_check_without_gpu():

@@ -207,6 +207,8 @@ __global__ void slab_reduce_kernel(const float* __restrict__ part, float* __rest
 
 extern "C" long long dcvic_conv_wgrad_workspace_floats(int N, int M, int Cx, int KH, int KW, int Hg, int* slabs_out) {
     // slabs: whole images split into row groups so that the launch has >= ~512 workgroups
+    if (slabs_out) *slabs_out = 0;
+    if (N <= 0 || M <= 0 || Cx <= 0 || KH <= 0 || KW <= 0 || Hg <= 0) return 0;
     const int mblocks = dcvic_cdiv(M, 128), cblocks = dcvic_cdiv(Cx, 32);
     const long long base = (long long)mblocks * cblocks * KH * N;
     int per_img = 1;
@@ -223,6 +225,8 @@ extern "C" int dcvic_conv_wgrad_f32(const float* G, long long g_bs, int M, int H
                                     void* stream) {
     DCVIC_CHECK_ARG(G && X && dW && workspace, "conv_wgrad: null pointer");
     DCVIC_CHECK_ARG(KW >= 1 && KW <= 5 && KH >= 1 && KH <= 5 && stride >= 1 && stride <= 4, "conv_wgrad: kernel %dx%d stride %d unsupported", KH, KW, stride);
+    DCVIC_CHECK_ARG(N > 0 && M > 0 && Cx > 0 && Hg > 0 && Wg > 0 && Hx > 0 && Wx > 0, "conv_wgrad: empty map N=%d M=%d Cx=%d Hg=%d Wg=%d Hx=%d Wx=%d",
+                    N, M, Cx, Hg, Wg, Hx, Wx);
     int slabs = 0;
     dcvic_conv_wgrad_workspace_floats(N, M, Cx, KH, KW, Hg, &slabs);
     WgradArgs a;
@@ -239,6 +243,8 @@ extern "C" int dcvic_conv_wgrad_f32(const float* G, long long g_bs, int M, int H
     const long long blocks = (long long)a.mblocks * a.cblocks * (rows_fused ? 1 : KH) * slabs;
     DCVIC_CHECK_ARG(blocks < (1ll << 31), "conv_wgrad: grid too large");
     const int xw = 31 * stride + KW;
+    // (stride 4 needs 65 792 .. 66 816 bytes, above 64 KiB: measured to launch on gfx950 without raising the dynamic-LDS limit,
+    //  tests/test_gpu_train_kernels.py covers it)
     const size_t lds = (size_t)2 * (128 * 33 + (rows_fused ? 3 : 1) * 32 * (xw | 1)) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
     if (rows_fused) {
@@ -338,6 +344,7 @@ __global__ __launch_bounds__(256) void ew_bwd_kernel(int op, float* __restrict__
 extern "C" int dcvic_ew_bwd_f32(int op, float* d, const float* g, const float* a, const float* b, long long len, float w, int act, int C, int HW,
                                 long long vec_bs, void* stream) {
     DCVIC_CHECK_ARG(d && len > 0 && op >= 0 && op <= 11, "ew_bwd: bad argument");
+    DCVIC_CHECK_ARG(op != 7 || (C > 0 && HW > 0), "ew_bwd: op 7 needs C=%d > 0 and HW=%d > 0", C, HW);
     ew_bwd_kernel<<<dcvic_cdiv(len, 256), 256, 0, (hipStream_t)stream>>>(op, d, g, a, b, len, w, act, C, HW, vec_bs);
     DCVIC_CHECK_LAUNCH("ew_bwd");
     return DCVIC_OK;
@@ -464,6 +471,7 @@ extern "C" int dcvic_groupnorm_bwd_f32(const float* x, long long x_bs, const flo
                                        const float* gamma, const float* beta, float* dgamma_part, float* dbeta_part, int N, int C, int HW,
                                        int groups, float eps, int act, void* stream) {
     DCVIC_CHECK_ARG(x && dy && dx && gamma && beta && dgamma_part && dbeta_part, "groupnorm_bwd: null pointer");
+    DCVIC_CHECK_ARG(N > 0 && C > 0 && HW > 0 && groups > 0, "groupnorm_bwd: N=%d C=%d HW=%d groups=%d", N, C, HW, groups);
     DCVIC_CHECK_ARG(C % groups == 0 && (act == DCVIC_ACT_NONE || act == DCVIC_ACT_SWISH), "groupnorm_bwd: C=%d groups=%d act=%d", C, groups, act);
     DCVIC_CHECK_ARG(C / groups <= 64, "groupnorm_bwd: %d channels per group (at most 64)", C / groups);
     groupnorm_bwd_kernel<<<N * groups, 512, 0, (hipStream_t)stream>>>(x, x_bs, dy, dy_bs, dx, dx_bs, gamma, beta, dgamma_part, dbeta_part, C, HW,
@@ -519,7 +527,7 @@ __global__ __launch_bounds__(256) void layernorm_c_bwd_kernel(const float* __res
 extern "C" int dcvic_layernorm_c_bwd_blocks(int N, int HW) { return dcvic_cdiv((long long)N * HW, 256); }
 extern "C" int dcvic_layernorm_c_bwd_f32(const float* x, const float* dy, float* dx, const float* gamma, float* part, int N, int C, int HW,
                                          float eps, void* stream) {
-    DCVIC_CHECK_ARG(x && dy && dx && gamma && part && C <= 1024, "layernorm_c_bwd: bad argument");
+    DCVIC_CHECK_ARG(x && dy && dx && gamma && part && N > 0 && C > 0 && C <= 1024 && HW > 0, "layernorm_c_bwd: bad argument");
     const int blocks = dcvic_cdiv((long long)N * HW, 256);
     layernorm_c_bwd_kernel<<<blocks, 256, (size_t)8 * C * sizeof(float), (hipStream_t)stream>>>(x, dy, dx, gamma, part, C, HW, N * HW, eps);
     DCVIC_CHECK_LAUNCH("layernorm_c_bwd");
@@ -538,7 +546,7 @@ __global__ __launch_bounds__(256) void softmax_c_bwd_kernel(const float* __restr
     for (int c = 0; c < C; ++c) { const long long i = base + (long long)c * Pn; dS[i] = scale * P[i] * (dP[i] - dot); }
 }
 extern "C" int dcvic_softmax_c_bwd_f32(const float* P, const float* dP, float* dS, int N, int C, int Pn, float scale, void* stream) {
-    DCVIC_CHECK_ARG(P && dP && dS && N > 0 && N <= 65535, "softmax_c_bwd: bad argument");
+    DCVIC_CHECK_ARG(P && dP && dS && N > 0 && N <= 65535 && C > 0 && Pn > 0, "softmax_c_bwd: bad argument");
     dim3 grid(dcvic_cdiv(Pn, 256), N);
     softmax_c_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(P, dP, dS, C, Pn, scale);
     DCVIC_CHECK_LAUNCH("softmax_c_bwd");
@@ -658,7 +666,9 @@ __global__ __launch_bounds__(64) void swin_bias_grad_kernel(const float* __restr
 extern "C" int dcvic_swin_attn_bwd_f32(const float* qkv, const float* dout, float* dqkv, const float* table, float* dtable, float* dS_workspace,
                                        int N, int C, int H, int W, int heads, int ws, int shift, int accumulate, void* stream) {
     DCVIC_CHECK_ARG(qkv && dout && dqkv && table && dtable && dS_workspace, "swin_attn_bwd: null pointer");
-    DCVIC_CHECK_ARG(ws == 8 && C % heads == 0 && C / heads <= 16 && H % ws == 0 && W % ws == 0, "swin_attn_bwd: ws=%d C=%d heads=%d", ws, C, heads);
+    DCVIC_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && heads > 0, "swin_attn_bwd: N=%d C=%d H=%d W=%d heads=%d", N, C, H, W, heads);
+    DCVIC_CHECK_ARG(ws == 8 && C % heads == 0 && C / heads <= 16 && H % ws == 0 && W % ws == 0 && shift >= 0 && shift < ws,
+                    "swin_attn_bwd: ws=%d C=%d heads=%d H=%d W=%d shift=%d", ws, C, heads, H, W, shift);
     const int nwin = N * (H / ws) * (W / ws);
     swin_attn_bwd_kernel<<<nwin * heads, 64, 0, (hipStream_t)stream>>>(qkv, dout, dqkv, table, dS_workspace, C, H, W, heads, ws, shift);
     DCVIC_CHECK_LAUNCH("swin_attn_bwd");
@@ -693,7 +703,7 @@ __global__ void loss_final_kernel(const double* __restrict__ part, int n, double
 // out[0] = scale * sum_i f(a[i], b[i] | t); kind 0: (a-b)^2, 1: BCE-with-logits(a, target t), 2: a^2, 3: a.  workspace: 1024 doubles
 extern "C" int dcvic_reduce_loss_f32(int kind, const float* a, const float* b, long long len, int target, double scale, float* out,
                                      double* workspace, void* stream) {
-    DCVIC_CHECK_ARG(a && out && workspace && len > 0 && kind >= 0 && kind <= 3, "reduce_loss: bad argument");
+    DCVIC_CHECK_ARG(a && out && workspace && len > 0 && kind >= 0 && kind <= 3 && (kind != 0 || b), "reduce_loss: bad argument");
     const int blocks = (int)min((long long)1024, (long long)dcvic_cdiv(len, 256));
     loss_partial_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(kind, a, b, len, target, workspace);
     loss_final_kernel<<<1, 64, 0, (hipStream_t)stream>>>(workspace, blocks, scale, out);
@@ -721,7 +731,7 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
 }
 extern "C" int dcvic_cross_entropy_f32(const float* logits, const int64_t* target, float* nll, float* dlogits, int N, int C, int HW, float w,
                                        void* stream) {
-    DCVIC_CHECK_ARG(logits && target && nll && N > 0 && N <= 65535, "cross_entropy: bad argument");
+    DCVIC_CHECK_ARG(logits && target && nll && N > 0 && N <= 65535 && C > 0 && HW > 0, "cross_entropy: bad argument");
     dim3 grid(dcvic_cdiv(HW, 256), N);
     ce_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(logits, target, nll, dlogits, C, HW, w);
     DCVIC_CHECK_LAUNCH("cross_entropy");
@@ -780,7 +790,7 @@ __global__ __launch_bounds__(256) void resample2_kernel(int down, const float* _
     }
 }
 extern "C" int dcvic_resample2_f32(int down, const float* in, float* out, long long planes, int Hlow, int Wlow, void* stream) {
-    DCVIC_CHECK_ARG(in && out && planes > 0, "resample2: bad argument");
+    DCVIC_CHECK_ARG(in && out && planes > 0 && Hlow > 0 && Wlow > 0, "resample2: bad argument");
     const long long total = down ? planes * Hlow * Wlow : planes * 4 * Hlow * Wlow;
     resample2_kernel<<<dcvic_cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(down, in, out, planes, Hlow, Wlow);
     DCVIC_CHECK_LAUNCH("resample2");
@@ -818,7 +828,7 @@ __global__ __launch_bounds__(256) void s2d_kernel(const float* __restrict__ in, 
 }
 extern "C" int dcvic_s2d_f32(const float* in, float* out, long long planes, int H, int W, int r, int pad, int Ho, int Wo, int inverse,
                              void* stream) {
-    DCVIC_CHECK_ARG(in && out && planes > 0 && r >= 1 && Ho >= 1 && Wo >= 1, "s2d: bad argument");
+    DCVIC_CHECK_ARG(in && out && planes > 0 && H > 0 && W > 0 && r >= 1 && pad >= 0 && Ho >= 1 && Wo >= 1, "s2d: bad argument");
     const long long total = inverse ? planes * H * W : planes * r * r * Ho * Wo;
     s2d_kernel<<<dcvic_cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(in, out, planes, H, W, r, pad, Ho, Wo, inverse);
     DCVIC_CHECK_LAUNCH("s2d");
@@ -897,7 +907,7 @@ __global__ __launch_bounds__(256) void lpips_tap_kernel(const float* __restrict_
 }
 extern "C" int dcvic_lpips_tap_f32(const float* f0, const float* f1, const float* w, float* pix, float* df1, int N, int C, int HW, float gscale,
                                    void* stream) {
-    DCVIC_CHECK_ARG(f0 && f1 && w && pix && N > 0 && N <= 65535, "lpips_tap: bad argument");
+    DCVIC_CHECK_ARG(f0 && f1 && w && pix && N > 0 && N <= 65535 && C > 0 && HW > 0, "lpips_tap: bad argument");
     dim3 grid(dcvic_cdiv(HW, 256), N);
     lpips_tap_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(f0, f1, w, pix, df1, C, HW, gscale);
     DCVIC_CHECK_LAUNCH("lpips_tap");

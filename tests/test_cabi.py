@@ -127,6 +127,98 @@ def test_rate_and_copy_argument_checks_without_gpu():
     _run_without_gpu(_ARG_CHECKS)
 
 
+
+# Every case breaks one rule of one training-step entry point (csrc/train.hip) and keeps the others valid.  A divisor of zero
+# must be rejected before the host divides by it (a SIGFPE would end the child); a zero size must not reach a launch.
+_TRAIN_ARG_CHECKS = r"""
+F = C.c_float
+# conv_wgrad(G, g_bs, M, Hg, Wg, X, x_bs, Cx, Hx, Wx, N, KH, KW, stride, pt, pl, dW, accumulate, workspace, stream); baseline:
+# N = 2, 16 -> 8 channels, 3x3 / stride 1 / pad 1 on 8 x 8 maps
+def wg(M=8, Hg=8, Wg=8, Cx=16, Hx=8, Wx=8, N=2, KH=3, KW=3, stride=1):
+    return L.dcvic_conv_wgrad_f32(P, LL(M * Hg * Wg), M, Hg, Wg, P, LL(Cx * Hx * Wx), Cx, Hx, Wx, N, KH, KW, stride, 1, 1, P, 0, P, None)
+for kw in (dict(N=0), dict(M=0), dict(Cx=0), dict(Hg=0), dict(Wg=0), dict(Hx=0), dict(Wx=0)):
+    err(wg(**kw), "conv_wgrad", "empty map")
+for kw in (dict(KW=0), dict(KW=6), dict(KH=0), dict(KH=6), dict(stride=0), dict(stride=5)):
+    err(wg(**kw), "conv_wgrad", "unsupported")
+slabs = C.c_int(-1)
+for args in ((0, 8, 16, 3, 3, 8), (2, 0, 16, 3, 3, 8), (2, 8, 0, 3, 3, 8), (2, 8, 16, 0, 3, 8), (2, 8, 16, 3, 0, 8), (2, 8, 16, 3, 3, 0)):
+    assert L.dcvic_conv_wgrad_workspace_floats(*args, C.byref(slabs)) == 0 and slabs.value == 0, args
+assert L.dcvic_conv_wgrad_workspace_floats(2, 8, 16, 3, 3, 8, C.byref(slabs)) == slabs.value * 8 * 16 * 9 and slabs.value >= 2
+
+# chan_reduce(a, a_bs, b, b_bs, out, N, C, HW, stream) / sum_rows(in, out, rows, len, accumulate, stream)
+for n, c, hw in ((0, 4, 16), (2, 0, 16), (2, 4, 0)):
+    err(L.dcvic_chan_reduce_f32(P, LL(64), None, LL(0), P, n, c, hw, None), "chan_reduce")
+err(L.dcvic_sum_rows_f32(P, P, 0, LL(16), 0, None), "sum_rows")
+err(L.dcvic_sum_rows_f32(P, P, 2, LL(0), 0, None), "sum_rows")
+
+# ew_bwd(op, d, g, a, b, len, w, act, C, HW, vec_bs, stream)
+for op in (-1, 12):
+    err(L.dcvic_ew_bwd_f32(op, P, P, P, P, LL(64), F(1), 0, 4, 16, LL(0), None), "ew_bwd")
+err(L.dcvic_ew_bwd_f32(1, P, P, P, P, LL(0), F(1), 0, 4, 16, LL(0), None), "ew_bwd")
+err(L.dcvic_ew_bwd_f32(7, P, P, P, P, LL(64), F(1), 0, 0, 16, LL(0), None), "ew_bwd", "op 7")
+err(L.dcvic_ew_bwd_f32(7, P, P, P, P, LL(64), F(1), 0, 4, 0, LL(0), None), "ew_bwd", "op 7")
+
+# groupnorm_bwd(x, x_bs, dy, dy_bs, dx, dx_bs, gamma, beta, dgamma_part, dbeta_part, N, C, HW, groups, eps, act, stream)
+def gnb(N=2, Cc=64, HW=16, groups=32, act=3):
+    bs = LL(Cc * HW)
+    return L.dcvic_groupnorm_bwd_f32(P, bs, P, bs, P, bs, P, P, P, P, N, Cc, HW, groups, F(1e-6), act, None)
+for kw in (dict(groups=0), dict(N=0), dict(Cc=0), dict(HW=0)):
+    err(gnb(**kw), "groupnorm_bwd")
+err(gnb(groups=7), "groupnorm_bwd", "groups=7")                       # C % groups
+err(gnb(Cc=130, groups=2), "groupnorm_bwd", "65 channels per group")  # at most 64
+err(gnb(act=1), "groupnorm_bwd", "act=1")                            # only none / swish
+
+# layernorm_c_bwd(x, dy, dx, gamma, part, N, C, HW, eps, stream)
+for n, c, hw in ((0, 8, 16), (2, 0, 16), (2, 8, 0), (2, 1025, 16)):
+    err(L.dcvic_layernorm_c_bwd_f32(P, P, P, P, P, n, c, hw, F(1e-6), None), "layernorm_c_bwd")
+# softmax_c_bwd(P, dP, dS, N, C, Pn, scale, stream)
+for n, c, pn in ((0, 4, 16), (65536, 4, 16), (2, 0, 16), (2, 4, 0)):
+    err(L.dcvic_softmax_c_bwd_f32(P, P, P, n, c, pn, F(1), None), "softmax_c_bwd")
+
+# swin_attn_bwd(qkv, dout, dqkv, table, dtable, dS_ws, N, C, H, W, heads, ws, shift, accumulate, stream)
+def swb(N=1, Cc=32, H=16, W=16, heads=2, ws=8, shift=0):
+    return L.dcvic_swin_attn_bwd_f32(P, P, P, P, P, P, N, Cc, H, W, heads, ws, shift, 0, None)
+for kw in (dict(heads=0), dict(N=0), dict(Cc=0), dict(H=0), dict(W=0)):
+    err(swb(**kw), "swin_attn_bwd")
+err(swb(ws=4), "swin_attn_bwd", "ws=4")
+err(swb(heads=1), "swin_attn_bwd", "heads=1")          # head dim 32 > 16
+err(swb(heads=3), "swin_attn_bwd", "heads=3")          # C % heads
+err(swb(H=12), "swin_attn_bwd", "H=12")                # H % ws
+err(swb(shift=8), "swin_attn_bwd", "shift=8")
+err(swb(shift=-4), "swin_attn_bwd", "shift=-4")
+
+# reduce_loss(kind, a, b, len, target, scale, out, workspace, stream) / cross_entropy(logits, target, nll, dlogits, N, C, HW, w, stream)
+D = C.c_double
+for kind, b, ln in ((-1, P, 16), (4, P, 16), (0, P, 0), (0, None, 16)):
+    err(L.dcvic_reduce_loss_f32(kind, P, b, LL(ln), 0, D(1), P, P, None), "reduce_loss")
+for n, c, hw in ((0, 4, 16), (2, 0, 16), (2, 4, 0)):
+    err(L.dcvic_cross_entropy_f32(P, P, P, P, n, c, hw, F(1), None), "cross_entropy")
+
+# adam_step(p, g, m, v, len, lr, b1, b2, eps, step, gscale, stream) / clip_scale(sumsq, max_norm, out, stream)
+err(L.dcvic_adam_step_f32(P, P, P, P, LL(16), F(1e-3), F(0.9), F(0.999), F(1e-8), 0, None, None), "adam")
+err(L.dcvic_adam_step_f32(P, P, P, P, LL(0), F(1e-3), F(0.9), F(0.999), F(1e-8), 1, None, None), "adam")
+err(L.dcvic_clip_scale_f32(None, F(1), P, None), "clip_scale")
+
+# resample2(down, in, out, planes, Hlow, Wlow, stream) / s2d(in, out, planes, H, W, r, pad, Ho, Wo, inverse, stream) /
+# maxpool3s2(x, y, argmax, dy, dx, planes, H, W, stream) / lpips_tap(f0, f1, w, pix, df1, N, C, HW, gscale, stream)
+for pl, h, w in ((0, 4, 4), (2, 0, 4), (2, 4, 0)):
+    err(L.dcvic_resample2_f32(1, P, P, LL(pl), h, w, None), "resample2")
+for a in ((0, 8, 8, 2, 0, 4, 4), (2, 0, 8, 2, 0, 4, 4), (2, 8, 0, 2, 0, 4, 4), (2, 8, 8, 0, 0, 4, 4), (2, 8, 8, 2, -1, 4, 4),
+          (2, 8, 8, 2, 0, 0, 4)):
+    err(L.dcvic_s2d_f32(P, P, LL(a[0]), *a[1:], 0, None), "s2d")
+for pl, h, w in ((0, 8, 8), (2, 2, 8), (2, 8, 2)):
+    err(L.dcvic_maxpool3s2_f32(P, P, P, None, None, LL(pl), h, w, None), "maxpool")
+for n, c, hw in ((0, 64, 16), (65536, 64, 16), (2, 0, 16), (2, 64, 0)):
+    err(L.dcvic_lpips_tap_f32(P, P, P, P, None, n, c, hw, F(1), None), "lpips_tap")
+print("CHECKS_OK")
+"""
+
+
+def test_train_argument_checks_without_gpu():
+    """The training-step entry points reject zero sizes and divisors, out-of-range kernels / ops / steps and unsupported
+    layer shapes in their host-side checks, before any launch and without dividing by zero (see _TRAIN_ARG_CHECKS)."""
+    _run_without_gpu(_TRAIN_ARG_CHECKS)
+
 # Every case breaks exactly one rule of one convolution entry point and keeps every other argument valid, so the order in which an
 # entry point runs its checks does not matter.  Baseline layer: N = 2, one 16-channel 8 x 8 source, 16 output channels (3 for thin).
 _CONV_ARG_CHECKS = r"""

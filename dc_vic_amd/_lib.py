@@ -75,6 +75,8 @@ SYMBOLS = [
     "dcvic_resample2_f32", "dcvic_s2d_f32", "dcvic_maxpool3s2_f32", "dcvic_lpips_tap_f32",
     # full-reference metrics (csrc/metrics.hip)
     "dcvic_l2pool_f32", "dcvic_pair_moments_workspace_doubles", "dcvic_pair_moments_f64", "dcvic_dists_score_f64", "dcvic_lpips_score_f64",
+    # HiFiC patch FID (csrc/fid.hip)
+    "dcvic_fid_patch_resize_f32", "dcvic_fid_pool3_f32", "dcvic_fid_mean_hw_f32", "dcvic_fid_stats_accum_f64",
 ]
 
 _lib = None

@@ -409,6 +409,26 @@ int dcvic_dists_score_f64(const double* mom, long long mom_bs, const double* alp
                           void* stream);
 int dcvic_lpips_score_f64(const double* mom, int N, int taps, double* out, void* stream);
 
+/* HiFiC patch FID (scripts/calc_metrics.py:220-320 computes it through pytorch-fid on 256 x 256 patch PNGs; csrc/fid.hip).  FID-Inception
+ * (pytorch-fid's FIDInceptionV3, pool3) restated; parity with the pytorch_fid package unpinned (it is not in the reference tree):
+ *   fid_patch_resize: replaces ToTensor + F.interpolate(size=(S, S), mode="bilinear", align_corners=False) + 2 x - 1 of
+ *                     pytorch-fid's InceptionV3.forward, applied to crop_hific_fid_patches' patches (written to PNG and read back in the
+ *                     reference, which is lossless).  img: one u8 H x W x 3 image on the device; origins: B device (y0, x0) int pairs;
+ *                     out[b * out_bs + c * S * S + ...] = the ph x pw patch at origin b, resized.  Computed in fp64, rounded once;
+ *   fid_pool3:        mode 0 = MaxPool2d(3, 2), mode 1 = F.avg_pool2d(3, 1, 1, count_include_pad=False), mode 2 = F.max_pool2d(3, 1, 1)
+ *                     of the Inception blocks, on N images of C dense H x W planes with batch strides x_bs / y_bs (y may be a channel
+ *                     slice of a block's concatenated output);
+ *   fid_mean_hw:      AdaptiveAvgPool2d(1) (the pool3 features): y[n * y_bs + c] = mean of plane (n, c), HW elements;
+ *   fid_stats_accum:  the feature statistics of pytorch-fid's calculate_activation_statistics (np.mean, np.cov) as running fp64 sums of
+ *                     one batch of B rows of D fp32 features (row stride f_rs): sum[j] += sum_b F[b][j], gram[i * D + j] += sum_b F[b][i]
+ *                     F[b][j] for i <= j only.  Fixed order, no atomics: bitwise reproducible.
+ * Every value depends on its own patch only: the features of a patch do not depend on its batch. */
+int dcvic_fid_patch_resize_f32(const unsigned char* img, int H, int W, const int* origins, int B, int ph, int pw, int S, float* out,
+                               long long out_bs, void* stream);
+int dcvic_fid_pool3_f32(int mode, const float* x, long long x_bs, int N, int C, int H, int W, float* y, long long y_bs, void* stream);
+int dcvic_fid_mean_hw_f32(const float* x, long long x_bs, int N, int C, int HW, float* y, long long y_bs, void* stream);
+int dcvic_fid_stats_accum_f64(const float* F, long long f_rs, int B, int D, double* sum, double* gram, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,9 +11,12 @@ dataset with run_model(is_train=False) at that (beta_rate, beta_vq) (:119-155), 
 img_utils.imwrite), `_rate_summary.csv` and `_avg_bitrate.json` per setting, scores `alpha * PSNR - FID` (Eq. 13, :205) and
 writes `target_rate_*/result.csv` (sorted by score) and `beta_selection_results.csv`.
 
-FID needs the pytorch_fid Inception weights, which cannot be fetched offline: when they are unavailable the `fid` column is
-NaN and the score falls back to `alpha * PSNR` (a message says so); `--fid_csv` lets an external FID tool supply
-`beta_vq,target_rate,fid` rows instead.  `--synthetic_weights` replaces --model_path by the deterministic synthetic weights.
+FID needs pytorch-fid's Inception weights, which cannot be fetched offline: `--inception_path` names the file
+(pt_inception-2015-12-05-6726825d.pth), and FID is then computed on the device as scripts/calc_metrics.py does (HiFiC patch FID,
+dc_vic_amd.fid), with the real set's statistics computed once for all settings.  Without it, or under 50 images (where the
+reference would fail), the `fid` column is NaN and the score falls back to `alpha * PSNR` (a message says so).  `--fid_csv` lets
+an external FID tool supply `beta_vq,target_rate,fid` rows instead, and takes precedence.  `--synthetic_weights` replaces
+--model_path by the deterministic synthetic weights.
 Per-image bpp comes from the kernel-side per-image bit counts (`bits_per_image`), not from a second pass over the
 likelihood maps (calc_batch_bpp :96-104 computes the same quantity).
 """
@@ -34,7 +37,7 @@ import torch
 sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.append(os.path.dirname(os.path.abspath(__file__)))
 from binary_rate_search import batches, load_dataset  # noqa: E402
-from calc_metrics import average_psnr  # noqa: E402
+from calc_metrics import FID_MIN_IMAGES, average_psnr, fid_metric, fid_statistics  # noqa: E402
 from dc_vic_amd import BaseConfig, build_comp_model, ops  # noqa: E402
 from dc_vic_amd.io_pipeline import AsyncWriter, encode_png_u8  # noqa: E402
 
@@ -56,6 +59,8 @@ def arg_parse() -> dict:
     p.add_argument("-d", "--device", type=str, default="cuda:0")
     p.add_argument("--synthetic_weights", action="store_true")
     p.add_argument("--fid_csv", type=str, default=None, help="optional csv (beta_vq,target_rate,fid) from an external FID tool")
+    p.add_argument("--inception_path", type=str, default=None,
+                   help="pytorch-fid's FID Inception state dict (pt_inception-2015-12-05-6726825d.pth) to compute FID on the device")
     return vars(p.parse_args())
 
 
@@ -86,21 +91,31 @@ def save_reconstructions(model, items, names, bs, save_dir, beta_vq, beta_rate) 
     return avg_bpp
 
 
-def try_fid(real_paths, fake_paths, device):
-    """calc_metrics.py:220-320 (HiFiC-style patch FID).  Needs pytorch_fid + its Inception weights."""
-    try:
-        import pytorch_fid  # noqa: F401
-    except ImportError:
+def try_fid(real_paths, fake_paths, device, inception=None, real_stats=None):
+    """calc_metrics.py:220-320 (HiFiC-style patch FID) on the device (scripts/calc_metrics.fid_metric); None without
+    --inception_path, or under 50 images (with the reference's message).  `real_stats`: a dict that caches the real set's (mu, sigma)
+    per list of real images, so it is computed once for every (target_rate, beta_vq) setting."""
+    if inception is None or len(real_paths) < FID_MIN_IMAGES:
+        if inception is not None:
+            print(f"[beta_selection] num_img (={len(real_paths)}) is too small to calc FID", file=sys.stderr)
         return None
-    return None            # the weights are a remote download (pt_inception-2015-12-05): unavailable offline
+    key = tuple(real_paths)
+    if real_stats is not None and key not in real_stats:
+        real_stats[key] = fid_statistics(inception, real_paths, device)
+        print(f"[beta_selection] FID: statistics of the {len(real_paths)} real images computed", flush=True)
+    return fid_metric(inception, real_paths, fake_paths, device, real_stats=None if real_stats is None else real_stats[key])
 
 
 def main() -> None:
     a = arg_parse()
-    opt = BaseConfig.fromfile(a["config_path"], {k: v for k, v in a.items() if k not in ("synthetic_weights", "fid_csv")})
+    opt = BaseConfig.fromfile(a["config_path"], {k: v for k, v in a.items() if k not in ("synthetic_weights", "fid_csv", "inception_path")})
     ck = opt["subnet"]["vq_model"].get("ckpt_path")
     if ck and not os.path.exists(ck):
         opt["subnet"]["vq_model"]["ckpt_path"] = None
+    inception = None
+    if a["inception_path"]:                       # checked before any image is read or reconstructed
+        from dc_vic_amd.fid import FIDInception
+        inception = FIDInception.from_file(a["inception_path"])
     os.makedirs(a["save_dir"], exist_ok=True)
     assert os.path.exists(a["dataset_root"]), f'dataset_root "{a["dataset_root"]}" does not exist.'
     items = load_dataset(a["dataset_root"])
@@ -119,6 +134,7 @@ def main() -> None:
 
     selection = []
     warned = False
+    real_stats = {}
     for target_rate in a["target_rate"]:
         data = []
         save_dir = os.path.join(a["save_dir"], f"target_rate_{target_rate}")
@@ -138,7 +154,7 @@ def main() -> None:
             psnr = average_psnr(real, fake)
             fid = ext_fid.get((round(beta_vq, 4), round(target_rate, 4)))
             if fid is None:
-                fid = try_fid(real, fake, a["device"])
+                fid = try_fid(real, fake, a["device"], inception, real_stats)
             if fid is None:
                 if not warned:
                     print("[beta_selection] FID unavailable offline (Inception weights): score = alpha * PSNR; pass --fid_csv to add it", file=sys.stderr)

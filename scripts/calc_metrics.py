@@ -6,16 +6,21 @@ Same flags (--real_dir --fake_dir -d/--device) and the same output file `<fake_d
   * "bpp"  : read from `<fake_dir>/_avg_bitrate.json`, which scripts/compress.py wrote (calc_metrics.py:322-327);
   * "PSNR" : image-averaged PSNR over the sorted, name-matched *.png pairs, on RGB float32 in [0, 255]:
              20 log10(255) - 10 log10(mean squared error)  (calc_metrics.py:121-171), threads over images.
+  * "FID"  : with --inception_path (pytorch-fid's pt_inception-2015-12-05-6726825d.pth): HiFiC patch FID (calc_metrics.py:220-320) --
+             the 256 x 256 patches of `crop_hific_fid_patches` of both sets through FID-Inception (pool3, 2048-d) in batches of 100,
+             FID(fake, real) as calculate_fid_given_paths([fake, real]) -- computed by dc_vic_amd.fid on the device -d: patches are
+             cut and resized from each image uploaded once, and the fp64 feature statistics stay on the device.  Under 50 image pairs
+             FID is left out with the reference's message.
   * "LPIPS": with --lpips_path (a state dict of lpips.LPIPS(net='alex'), as scripts/train.py takes): LPIPS(fake, real) per image
              on RGB in [-1, 1] (ToTensor, Normalize(.5, .5)), computed by dc_vic_amd.metrics on the device -d (calc_metrics.py:174-196);
   * "DISTS": with --dists_path (a complete DISTS() state dict, or DISTS_pytorch's weights.pt {alpha, beta} plus --vgg16_path,
              torchvision's VGG16 state dict): DISTS(fake, real) per image on RGB in [0, 1] (ToTensor) (calc_metrics.py:198-215).
   Both are image means of per-image values at full resolution; images are batched by shape, and a value does not depend on its batch.
-  Weight files are loaded (torch.load weights_only=True) and checked before any image is read.  Parity with the lpips / DISTS_pytorch
-  packages is unpinned (restated architectures; see dc_vic_amd/metrics.py).
+  Weight files are loaded (torch.load weights_only=True) and checked before any image is read.  Parity with the pytorch_fid / lpips /
+  DISTS_pytorch packages is unpinned (restated architectures; see dc_vic_amd/fid.py and dc_vic_amd/metrics.py).
 A metric whose weights are not given is skipped with a message and absent from the json; without these flags nothing here touches
-torch or the GPU.  FID needs Inception weights and is always skipped.  The HiFiC FID patch cropper is provided
-(`crop_hific_fid_patches`, calc_metrics.py:307-320) because the patch sets it produces are what an external FID tool consumes.
+torch or the GPU.  The keys keep the reference's order: bpp, PSNR, FID, LPIPS, DISTS.  The HiFiC FID patch cropper is provided
+(`crop_hific_fid_patches`, calc_metrics.py:307-320) for external FID tools; it and the device path share `hific_patch_origins`.
 """
 from __future__ import annotations
 
@@ -64,18 +69,25 @@ def average_psnr(real_paths: List[str], fake_paths: List[str], workers: int = 8)
     return float(np.mean(vals))
 
 
+def hific_patch_origins(H: int, W: int, patch_size: int) -> np.ndarray:
+    """(y0, x0) of every HiFiC FID patch of an H x W image, in crop_hific_fid_patches' order (calc_metrics.py:307-320): the
+    non-overlapping p x p blocks in row-major order, then those of the image shifted by p // 2 in both directions."""
+    p = patch_size
+    o = p // 2
+    grids = []
+    for s, h, w in ((0, H, W), (o, H - o, W - o)):
+        ys, xs = np.meshgrid(s + p * np.arange(max(h, 0) // p), s + p * np.arange(max(w, 0) // p), indexing="ij")
+        grids.append(np.stack([ys.ravel(), xs.ravel()], axis=1))
+    return np.concatenate(grids, axis=0).astype(np.int64)
+
+
 def crop_hific_fid_patches(img: np.ndarray, patch_size: int) -> np.ndarray:
     """All non-overlapping p x p blocks of the image, plus those of the image shifted by p/2 in both directions."""
     p = patch_size
     H, W = img.shape[:2]
-
-    def blocks(a):
-        h, w = a.shape[0] // p * p, a.shape[1] // p * p
-        a = a[:h, :w]
-        return a.reshape(h // p, p, w // p, p, 3).transpose(0, 2, 1, 3, 4).reshape(-1, p, p, 3)
-
-    o = p // 2
-    return np.concatenate([blocks(img), blocks(img[o:, o:])], axis=0)
+    out = np.empty((0, p, p) + img.shape[2:], dtype=img.dtype)
+    org = hific_patch_origins(H, W, p)
+    return np.stack([img[y:y + p, x:x + p] for y, x in org]) if len(org) else out
 
 
 def retrieve_bitrate(fake_dir: str) -> float:
@@ -91,11 +103,15 @@ MAX_BATCH_PIXELS = 1 << 22
 MAX_BATCH_IMAGES = 16
 
 
-def load_metric_models(lpips_path: Optional[str], dists_path: Optional[str], vgg16_path: Optional[str]) -> Dict[str, object]:
+def load_metric_models(lpips_path: Optional[str], dists_path: Optional[str], vgg16_path: Optional[str],
+                       inception_path: Optional[str] = None) -> Dict[str, object]:
     """The networks of the metrics whose weights were given, on the host ({} without any: torch is not imported then)."""
     if vgg16_path and not dists_path:
         raise ValueError("--vgg16_path is only used by DISTS: give --dists_path (DISTS_pytorch's weights.pt) with it")
     models: Dict[str, object] = {}
+    if inception_path:
+        from dc_vic_amd.fid import FIDInception
+        models["FID"] = FIDInception.from_file(inception_path)
     if lpips_path:
         import torch
         from dc_vic_amd.metrics import load_lpips
@@ -104,6 +120,58 @@ def load_metric_models(lpips_path: Optional[str], dists_path: Optional[str], vgg
         from dc_vic_amd.metrics import DISTSVGG
         models["DISTS"] = DISTSVGG.from_files(vgg16_path=vgg16_path, dists_path=dists_path)
     return models
+
+
+# HiFiC patch FID (calc_metrics.py:220-320): 256 x 256 patches, pytorch-fid batches of 100, at least 50 image pairs
+FID_PATCH = 256
+FID_BATCH_SIZE = 100
+FID_MIN_IMAGES = 50
+
+
+def read_u8(path: str) -> np.ndarray:
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+def _prefetch(fn, items, depth: int = 4):
+    """fn(item) for each item in order, up to `depth` ahead on worker threads (image decoding overlaps the device work)."""
+    from collections import deque
+    with ThreadPoolExecutor(max_workers=depth) as ex:
+        q = deque()
+        for it in items:
+            q.append(ex.submit(fn, it))
+            if len(q) > depth:
+                yield q.popleft().result()
+        while q:
+            yield q.popleft().result()
+
+
+def fid_statistics(model, paths: List[str], device: str, patch: int = FID_PATCH, batch: int = FID_BATCH_SIZE):
+    """(mu, sigma) in fp64 of the pool3 features of every HiFiC patch of the images, computed on the device."""
+    import torch
+    from dc_vic_amd.fid import PatchFeatures
+    dev = torch.device(device)
+    torch.cuda.set_device(dev)
+    model.to(dev)
+
+    def load(path):
+        img = read_u8(path)
+        return img, hific_patch_origins(img.shape[0], img.shape[1], patch)
+
+    return PatchFeatures(model, dev, batch, patch).statistics(_prefetch(load, paths)).mu_sigma()
+
+
+def fid_metric(model, real_paths: List[str], fake_paths: List[str], device: str, real_stats=None) -> Optional[float]:
+    """FID(fake patches, real patches) as calculate_fid_given_paths([fake, real]) takes it; None (with the reference's message) under
+    50 image pairs.  `real_stats`: the real set's (mu, sigma) when already computed."""
+    from dc_vic_amd.fid import frechet_distance
+    if len(real_paths) < FID_MIN_IMAGES:
+        print(f"[calc_metrics] num_img (={len(real_paths)}) is too small to calc FID", file=sys.stderr)
+        return None
+    mu1, s1 = fid_statistics(model, fake_paths, device)
+    mu2, s2 = real_stats if real_stats is not None else fid_statistics(model, real_paths, device)
+    return frechet_distance(mu1, s1, mu2, s2)
 
 
 def perceptual_metrics(models: Dict[str, object], real_paths: List[str], fake_paths: List[str], device: str) -> Dict[str, float]:
@@ -148,14 +216,21 @@ def main(argv=None):
     ap.add_argument("--dists_path", type=str, default=None,
                     help="DISTS_pytorch weights.pt ({alpha, beta}; needs --vgg16_path) or a complete DISTS() state dict")
     ap.add_argument("--vgg16_path", type=str, default=None, help="torchvision VGG16 ImageNet state dict (features.*) for --dists_path")
+    ap.add_argument("--inception_path", type=str, default=None,
+                    help="pytorch-fid's FID Inception state dict (pt_inception-2015-12-05-6726825d.pth; weights_only load) for FID")
     a = ap.parse_args(argv)
-    models = load_metric_models(a.lpips_path, a.dists_path, a.vgg16_path)
+    models = load_metric_models(a.lpips_path, a.dists_path, a.vgg16_path, a.inception_path)
     out = {"bpp": retrieve_bitrate(a.fake_dir)}
     real, fake = get_real_fake_path_list(a.real_dir, a.fake_dir)
     out["PSNR"] = average_psnr(real, fake)
     print(f"{len(real)} images: PSNR: {out['PSNR']:.4}")
-    if models:
-        out.update(perceptual_metrics(models, real, fake, a.device))
+    if "FID" in models:
+        v = fid_metric(models["FID"], real, fake, a.device)
+        if v is not None:
+            out["FID"] = v
+    perceptual = {k: m for k, m in models.items() if k != "FID"}
+    if perceptual:
+        out.update(perceptual_metrics(perceptual, real, fake, a.device))
     for name in ("FID", "LPIPS", "DISTS"):
         if name not in models:
             print(f"[calc_metrics] {name} skipped: its pretrained network weights cannot be fetched offline", file=sys.stderr)

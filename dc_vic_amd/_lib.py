@@ -61,6 +61,7 @@ SYMBOLS = [
     "dcvic_wino44_packed_bytes", "dcvic_wino44_pack_f32", "dcvic_conv3x3_wino44_f32",
     "dcvic_conv3x3_thin_applies", "dcvic_conv3x3_thin_f32",
     "dcvic_wino44_stats_tiles", "dcvic_conv3x3_wino44_stats_f32", "dcvic_groupnorm_part_f32",
+    "dcvic_wino44_ups_packed_bytes", "dcvic_wino44_ups_pack_f32", "dcvic_conv3x3_wino44_ups_f32", "dcvic_conv3x3_wino44_ups_stats_f32",
     "dcvic_conv3x3_bf16_packed_bytes", "dcvic_conv3x3_bf16_mfma_shape", "dcvic_conv3x3_bf16_pack_f32", "dcvic_conv3x3_bf16_f32",
     "dcvic_bgemm_f32", "dcvic_attn_fused_f32", "dcvic_groupnorm_f32", "dcvic_layernorm_c_f32", "dcvic_softmax_c_f32", "dcvic_swin_attn_f32",
     "dcvic_ew_f32", "dcvic_chan_affine_f32", "dcvic_copy_planes_f32", "dcvic_copy_window_f32", "dcvic_absmax_f32", "dcvic_crop_clamp_f32",
@@ -101,6 +102,7 @@ def lib() -> C.CDLL:
     L.dcvic_wino_packed_bytes.restype = C.c_size_t
     L.dcvic_wino_ups_packed_bytes.restype = C.c_size_t
     L.dcvic_wino44_packed_bytes.restype = C.c_size_t
+    L.dcvic_wino44_ups_packed_bytes.restype = C.c_size_t
     L.dcvic_conv3x3_bf16_packed_bytes.restype = C.c_size_t
     L.dcvic_conv_wgrad_workspace_floats.restype = C.c_longlong
     L.dcvic_pair_moments_workspace_doubles.restype = C.c_longlong

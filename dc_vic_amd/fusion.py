@@ -121,7 +121,8 @@ class VqDecFusionModule(nn.Module):
                     m = self.fusion_modules[key]
                     dst = cat_bufs[key][:, m.cond_ch:]
                 # `part`: GroupNorm statistics of h from the F(4x4) epilogue of the block that produced it, while the next consumer is a
-                # GroupNorm over exactly that map (not after attention / SFT fusion / upsampling, not into a concat buffer)
+                # GroupNorm over exactly that map (not after attention / SFT fusion, not into a concat buffer); the Upsample's F(4x4)
+                # epilogue hands its statistics on the same way
                 to_cat = dst is not None and not has_attn
                 h = lvl.block[i_block](h, out=None if has_attn else dst, in_part=part, want_part=not has_attn and not to_cat)
                 part = None if (has_attn or to_cat) else lvl.block[i_block].out_part
@@ -131,8 +132,8 @@ class VqDecFusionModule(nn.Module):
                 h = self.fusion_modules[key](cat_bufs[key], w)
                 part = None
             if i_level != 0:
-                h = lvl.upsample(h)
-                part = None
+                h = lvl.upsample(h, want_part=True)               # the next level starts with a ResnetBlock's norm1 over h
+                part = lvl.upsample.out_part
         if vq_dec.give_pre_end:
             return h
         h = vq_dec.norm_out(h, act=ops.ACT_SWISH, out=h, part=part)

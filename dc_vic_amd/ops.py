@@ -75,6 +75,8 @@ def conv_kernel_name(variant: int) -> str:
         return "conv3x3_wino_ups_kernel(ConvKArgs)"
     if variant == 9104:
         return "conv3x3_wino44_kernel(ConvKArgs)"
+    if variant == 9105:
+        return "conv3x3_wino44_ups_kernel(ConvKArgs)"
     if variant in (9300, 9301):
         return f"void conv3x3_bf16_kernel<{'true' if variant == 9301 else 'false'}>(Bf16Args, ConvKArgs)"
     if 9200 <= variant < 9210:
@@ -97,8 +99,9 @@ def conv_kernel_name(variant: int) -> str:
 
 
 # MFMA flops a kernel EXECUTES per algorithmic (direct-convolution 2*MAC) flop: Winograd F(2x2,3x3) issues 16 multiplies per 2x2
-# outputs and input channel instead of 36, the upsample-structured form 9 of 36, F(4x4,3x3) 36 per 4x4 outputs instead of 144
-EXECUTED_FRACTION = {9100: 16.0 / 36.0, 9101: 9.0 / 36.0, 9104: 36.0 / 144.0}
+# outputs and input channel instead of 36, the upsample-structured form 9 of 36, F(4x4,3x3) 36 per 4x4 outputs instead of 144, its
+# upsample-structured form 25 of 144
+EXECUTED_FRACTION = {9100: 16.0 / 36.0, 9101: 9.0 / 36.0, 9104: 36.0 / 144.0, 9105: 25.0 / 144.0}
 
 
 def kernel_events_start() -> None:
@@ -151,11 +154,12 @@ THIN_MIN_PIXELS = int(os.environ.get("DCVIC_THIN_MIN_PIXELS", "16384"))   # full
 THIN_ENABLED = os.environ.get("DCVIC_THIN", "1") != "0"       # VALU kernels for the 3 -> 128 / 128 -> 3 layers (csrc/thin.hip)
 WINO44_MIN_BLOCKS = int(os.environ.get("DCVIC_WINO44_MIN_BLOCKS", "16"))   # workgroup tiles PER IMAGE below which F(2x2) / direct run
 WINO44_ENABLED = os.environ.get("DCVIC_WINO44", "1") != "0"   # F(4x4,3x3) for the layers that opted in (ConvPlan.wino44)
+WINO44_UPS_MAX_CIN = 256          # upsample-structured F(4x4): wider layers keep F(2x2) (its error bound, tests/test_gpu_wino44_ups.py)
 WINO_MIN_BLOCKS = int(os.environ.get("DCVIC_WINO_MIN_BLOCKS", "16"))   # workgroups PER IMAGE below which the direct kernels run
 BF16_KERNEL_VARIANT = 9300        # conv3x3_bf16_kernel<false>; 9301 with the fused x2 upsample
 # ConvPlan routes with a weight pack of their own: route -> (C-ABI name stem of dcvic_<stem>_packed_bytes / dcvic_<stem>_pack_f32, dtype)
 _ROUTE_PACKS = {"bf16": ("conv3x3_bf16", torch.bfloat16), "wino44": ("wino44", torch.float32), "wino": ("wino", torch.float32),
-                "wino_ups": ("wino_ups", torch.float32)}
+                "wino_ups": ("wino_ups", torch.float32), "wino44_ups": ("wino44_ups", torch.float32)}
 
 
 class ConvPlan:
@@ -167,7 +171,7 @@ class ConvPlan:
 
     wino = False          # set by the owner: Winograd F(2x2,3x3) allowed (no integer decision downstream of this layer)
     wino44 = False        # set by the owner: F(4x4,3x3) allowed too -- post-argmax layers only (3x the F(2x2) rounding error)
-    last_gn_part = None   # (partial statistics [N, Cout, n_pt, 2], n_pt) written by the last call when gn_stats was asked AND the F(4x4) kernel ran
+    last_gn_part = None   # (partial statistics [N, Cout, n_pt, 2], n_pt) written by the last call when gn_stats was asked AND an F(4x4) kernel ran
     bf16 = False          # set by the owner: bf16-MFMA kernel (csrc/conv_bf16.hip) when eligible -- decoder precision "bf16" only
     last_bf16 = False     # whether the last call ran on the bf16 kernel
     bf16_launches = 0     # calls that ran on the bf16 kernel / on the fp32 kernels (coverage record)
@@ -274,6 +278,11 @@ class ConvPlan:
         """F(4x4, 3x3) eligibility: Conv2d(k3, s1, p1) on 16 x 32-pixel tiles (_wino_fills)."""
         return self._is_3x3() and self._wino_fills(srcs, H, W, H, W, 16, WINO44_MIN_BLOCKS)
 
+    def _wino44_ups_ok(self, srcs, H: int, W: int) -> bool:
+        """Eligibility of the upsample-fused F(4x4, 3x3) (input H x W, output 2H x 2W): 16 x 32-pixel tiles of the output (_wino_fills),
+        and at most WINO44_UPS_MAX_CIN input channels (its fp32 error grows with Cin: 1.8e-5 of the output's max at 512 channels)."""
+        return self.Cin <= WINO44_UPS_MAX_CIN and self._wino_fills(srcs, H, W, 2 * H, 2 * W, 16, WINO44_MIN_BLOCKS)
+
     def _wino_ups_ok(self, srcs, H: int, W: int) -> bool:
         """Eligibility of the upsample-fused Winograd (input H x W, output 2H x 2W): as _wino_ok, on the output's tile grid."""
         return self._wino_fills(srcs, H, W, 2 * H, 2 * W, 8, WINO_MIN_BLOCKS)
@@ -306,7 +315,7 @@ class ConvPlan:
     def __call__(self, srcs, out: Optional[Tensor] = None, act: int = ACT_NONE, res: Optional[Tensor] = None,
                  affine: Optional[Tuple[Tensor, Tensor]] = None, out_hw: Optional[Tuple[int, int]] = None,
                  init: Optional[Tensor] = None, use_bias: bool = True, gn_stats: bool = False) -> Tensor:
-        """`gn_stats`: the caller's next op is a GroupNorm over exactly this output; when the launch runs on the F(4x4) kernel its epilogue
+        """`gn_stats`: the caller's next op is a GroupNorm over exactly this output; when the launch runs on an F(4x4) kernel its epilogue
         also writes the GroupNorm partial sums (self.last_gn_part, else None) and the GroupNorm skips its statistics pass."""
         self.last_gn_part = None
         self.last_bf16 = False
@@ -392,6 +401,18 @@ class ConvPlan:
         elif route == "wino":
             self._launch("conv3x3_wino", L.dcvic_conv3x3_wino_f32, (self.Cin, self.Cout, _p(self._packed("wino")), C.byref(io), st),
                          9100, N, H, W, H, W)
+        elif route == "wino44_ups":
+            # nearest x2 + conv3x3 as the 25-position structured F(4x4) (csrc/wino44_ups.hip)
+            packed = _p(self._packed("wino44_ups"))
+            if gn_stats and GN_FUSED_STATS:
+                n_pt = int(L.dcvic_wino44_stats_tiles(Hf, Wf))
+                part = torch.empty((N, self.Cout, n_pt, 2), dtype=torch.float32, device=out.device)
+                self.last_gn_part = (part, n_pt)
+                self._launch("conv3x3_wino44_ups_stats", L.dcvic_conv3x3_wino44_ups_stats_f32,
+                             (self.Cin, self.Cout, packed, C.byref(io), _p(part), st), 9105, N, H, W, Hf, Wf, ups=1)
+            else:
+                self._launch("conv3x3_wino44_ups", L.dcvic_conv3x3_wino44_ups_f32, (self.Cin, self.Cout, packed, C.byref(io), st),
+                             9105, N, H, W, Hf, Wf, ups=1)
         elif route == "wino_ups":
             # nearest x2 + conv3x3 as the 9-position structured Winograd (csrc/wino.hip) instead of four 2x2 phase convolutions
             self._launch("conv3x3_wino_ups", L.dcvic_conv3x3_wino_ups_f32, (self.Cin, self.Cout, _p(self._packed("wino_ups")), C.byref(io), st),
@@ -418,8 +439,8 @@ class ConvPlan:
         return out
 
     def _route(self, srcs, out, act, res, affine, out_hw, init, N: int, H: int, W: int) -> str:
-        """The kernel family of one call, first match in this order: "bf16", "thin", "wino44" (F(4x4)), "wino" (F(2x2)), "wino_ups"
-        (F(2x2) behind the x2 upsample), else "direct" (dcvic_conv2d_f32 per phase).  A "force" in .wino / .wino44 skips the tile-fill
+        """The kernel family of one call, first match in this order: "bf16", "thin", "wino44" (F(4x4)), "wino" (F(2x2)), "wino44_ups"
+        (F(4x4) behind the x2 upsample), "wino_ups" (F(2x2) behind it), else "direct" (dcvic_conv2d_f32 per phase).  A "force" in .wino / .wino44 skips the tile-fill
         test of that form only."""
         if self.bf16 and init is None and self._bf16_ok(srcs, out_hw):
             return "bf16"
@@ -435,8 +456,12 @@ class ConvPlan:
                 return "wino44"
             if self.wino == "force" or self._wino_ok(srcs, N, H, W):
                 return "wino"
-        elif self.ups_phases and self._w is not None and (self.wino == "force" or self._wino_ups_ok(srcs, H, W)):
-            return "wino_ups"
+        elif self.ups_phases and self._w is not None:
+            if self.wino44 and WINO44_ENABLED and act in (ACT_NONE, ACT_RELU, ACT_LRELU02) \
+                    and (self.wino44 == "force" or self._wino44_ups_ok(srcs, H, W)):
+                return "wino44_ups"
+            if self.wino == "force" or self._wino_ups_ok(srcs, H, W):
+                return "wino_ups"
         return "direct"
 
     def _packed(self, route: str) -> Tensor:

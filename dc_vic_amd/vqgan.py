@@ -117,9 +117,14 @@ class Upsample(nn.Module):
         super().__init__()
         assert with_conv
         self.conv = Conv2d(in_channels, in_channels, 3, 1, 1, upsample=True)
+        self.out_part = None
 
-    def forward(self, x: Tensor) -> Tensor:
-        return self.conv(x)
+    def forward(self, x: Tensor, want_part: bool = False) -> Tensor:
+        """`want_part`: a GroupNorm over exactly the output follows -- `self.out_part` then holds its statistics when the convolution ran
+        on the F(4x4) upsample kernel (None otherwise)."""
+        y = self.conv(x, gn_stats=want_part)
+        self.out_part = self.conv.take_gn_part()
+        return y
 
 
 class Encoder(nn.Module):
@@ -233,8 +238,8 @@ class Decoder(nn.Module):
                     h = self.up[i_level].attn[i_block](h)
                     part = None
             if i_level != 0:
-                h = self.up[i_level].upsample(h)
-                part = None
+                h = self.up[i_level].upsample(h, want_part=True)    # the next level starts with a ResnetBlock's norm1 over h
+                part = self.up[i_level].upsample.out_part
         if self.give_pre_end:
             return h
         h = self.norm_out(h, act=ops.ACT_SWISH, out=h, part=part)

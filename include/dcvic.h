@@ -174,6 +174,18 @@ int dcvic_conv3x3_wino44_f32(int Cin, int Cout, const float* packed, const dcvic
  * dcvic_groupnorm_part_f32.  Fixed summation order, no atomics. */
 int dcvic_wino44_stats_tiles(int H, int W);
 int dcvic_conv3x3_wino44_stats_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream);
+/* Nearest-x2 upsample + Conv2d(k3, s1, p1) (ldm Upsample, model.py:42-57) as a structured Winograd F(4x4, 3x3) (csrc/wino44_ups.hip):
+ * a 4x4 output tile aligned to 4 sees the upsampled rows [a, b, b, c, c, d]; with the points 0, +-1, +-3/2, inf one transformed row
+ * (and column) is zero, so 25 of the 36 positions carry data -- 1.5625 multiplies per output (dcvic_conv3x3_wino_ups_f32: 2.25).
+ * Replaces dcvic_conv3x3_wino_ups_f32 on the layers after the path's last integer decision only (the frozen VQGAN decoder), as
+ * dcvic_conv3x3_wino44_f32 does for the plain 3x3 layers.  io contract of dcvic_conv3x3_wino_ups_f32 (H x W = the LOW-resolution
+ * input, Hout = Hfull = 2H, Wout = Wfull = 2W, W % 4 == 0, every source a multiple of 8 channels), activation none / ReLU /
+ * LeakyReLU(0.2).  The _stats form also writes gn_part[N][Cout][n_pt][2] with n_pt = dcvic_wino44_stats_tiles(2H, 2W), the layout of
+ * dcvic_conv3x3_wino44_stats_f32, for dcvic_groupnorm_part_f32.  Deterministic and batch-invariant. */
+size_t dcvic_wino44_ups_packed_bytes(int Cin, int Cout);
+int dcvic_wino44_ups_pack_f32(const float* w, float* packed, int Cin, int Cout, void* stream);
+int dcvic_conv3x3_wino44_ups_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, void* stream);
+int dcvic_conv3x3_wino44_ups_stats_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream);
 /* Opt-in bf16 reconstruction (csrc/conv_bf16.hip): Conv2d(k3, s1, p1), with `upsample` behind a nearest x2 (ldm Upsample,
  * model.py:42-57), as an implicit GEMM on bf16 MFMA with fp32 accumulation.  Replaces, when the model is set to decoder precision bf16,
  * the same operators as dcvic_conv3x3_wino44_f32 / dcvic_conv3x3_wino_ups_f32 -- the frozen VQGAN decoder and the SFT fusion blocks:

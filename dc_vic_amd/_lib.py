@@ -78,6 +78,8 @@ SYMBOLS = [
     "dcvic_l2pool_f32", "dcvic_pair_moments_workspace_doubles", "dcvic_pair_moments_f64", "dcvic_dists_score_f64", "dcvic_lpips_score_f64",
     # HiFiC patch FID (csrc/fid.hip)
     "dcvic_fid_patch_resize_f32", "dcvic_fid_pool3_f32", "dcvic_fid_mean_hw_f32", "dcvic_fid_stats_accum_f64",
+    # MS-SSIM and PSNR (csrc/ssim.hip)
+    "dcvic_msssim_workspace_bytes", "dcvic_msssim_psnr_f64",
 ]
 
 _lib = None
@@ -107,6 +109,8 @@ def lib() -> C.CDLL:
     L.dcvic_conv_wgrad_workspace_floats.restype = C.c_longlong
     L.dcvic_pair_moments_workspace_doubles.restype = C.c_longlong
     L.dcvic_pair_moments_workspace_doubles.argtypes = [C.c_longlong, C.c_longlong]
+    L.dcvic_msssim_workspace_bytes.restype = C.c_longlong
+    L.dcvic_msssim_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     L.dcvic_tables_create_host.restype = C.c_void_p
     L.dcvic_rans_decoder_create_host.restype = C.c_void_p
     L.dcvic_tables_destroy_host.argtypes = [C.c_void_p]

@@ -443,18 +443,17 @@ class HyperpriorVicModel(BaseModel):
         return self.encoder(real_images, feat, **enc_kwargs)
 
     # ------------------------------------------------------------------ decode (276-288, 413-473)
-    def _decode(self, y_hat: Tensor, w: float, beta_rate, beta_vq, want_logits: bool = False):
+    def _decode(self, y_hat: Tensor, w: float, beta_rate, beta_vq, want_logits: bool = False, want_embed: bool = False):
+        """-> (img, idx), + logits with want_logits, + the estimator's predicted embedding (out_vq_latent) with want_embed."""
         N, _, yH, yW = y_hat.shape
         cat_bufs = self.fusion_module.alloc_cat_buffers(N, 2 * yH, 2 * yW, y_hat.device)
         feat_out = {k: cat_bufs[k][:, : self.fusion_module.fusion_modules[k].cond_ch] for k in cat_bufs}
         feat_1, _ = self.decoder.get_feats(y_hat, beta_1=beta_rate, beta_2=beta_vq, feat_out=feat_out)
-        _, logits = self.vq_estimator(feat_1)
+        embed, logits = self.vq_estimator(feat_1, want_embed=want_embed)
         pq = self.vq_model.post_quant_conv
         idx, lat = ops.argmax_lut(logits, self.vq_model.quantize.embedding.weight, pq.weight.reshape(pq.out_channels, -1).contiguous(), pq.bias)
         img = self.fusion_module(lat, None, self.vq_model.decoder, w=w, cat_bufs=cat_bufs)
-        if want_logits:
-            return img, idx, logits
-        return img, idx
+        return (img, idx) + ((logits,) if want_logits else ()) + ((embed,) if want_embed else ())
 
     def decode_split(self, y_hat: Tensor, fuse_w: float, **kwargs) -> Tensor:
         """hyperprior_vic_model.py:413-473: 32x32-latent windows (512 px), stride 16, centre regions stitched into a buffer pre-filled
@@ -562,10 +561,10 @@ class HyperpriorDualCondVicModel(HyperpriorVicModel):
         if max(x.shape[2:]) > SPLIT_DECODE_RESOLUTION:
             fake = self.decode_split(y_hat, w, beta_rate=beta_rate, beta_vq=beta_vq)
             out_idx = torch.zeros_like(gt_vq_indices)
-            logits = None
+            logits = embed = None
             vq_acc = 0.0
         else:
-            fake, out_idx, logits = self._decode(y_hat, w, beta_rate, beta_vq, want_logits=True)
+            fake, out_idx, logits, embed = self._decode(y_hat, w, beta_rate, beta_vq, want_logits=True, want_embed=True)
             vq_acc = float((out_idx.cpu() == gt_vq_indices.cpu()).float().mean())
         num_pixel = N * H * W
         bits = (e["bits_y"].double().sum() + e["bits_z"].double().sum()).item()
@@ -575,8 +574,35 @@ class HyperpriorDualCondVicModel(HyperpriorVicModel):
         return dict(real_images=real_c, fake_images=fake_c, y_hat=y_hat, z_hat=e["z_hat"], bpp=bpp, qbpp=bpp,
                     y_likelihood=e["y_likelihood"], z_likelihood=e["z_likelihood"], y_q_likelihood=e["y_likelihood"],
                     z_q_likelihood=e["z_likelihood"], gt_vq_latent=gt_vq_latent, gt_vq_indices=gt_vq_indices,
-                    out_vq_indices=out_idx, out_vq_logits=logits, vq_accuracy=vq_acc, beta_rate=beta_rate, beta_vq=beta_vq,
+                    out_vq_indices=out_idx, out_vq_logits=logits, out_vq_latent=embed, vq_accuracy=vq_acc, beta_rate=beta_rate, beta_vq=beta_vq,
                     bits_per_image=(e["bits_y"] + e["bits_z"]))
+
+    # ------------------------------------------------------------------ validation (442-480)
+    @torch.no_grad()
+    def validation(self, images: Sequence[Tensor], max_sample_size: int = 100, beta_rate: Optional[float] = None,
+                   beta_vq: Optional[float] = None) -> List[Dict]:
+        """One row {idx, bpp, psnr, ms_ssim, vq_acc, vq_mse} per image of `images` (host or device [1, 3, H, W] in [-1, 1], at most
+        max_sample_size, one at a time as the reference's batch-1 loader): bpp and vq_acc are run_model's, psnr and ms_ssim those of
+        metrics.ms_ssim_psnr on its cropped real / fake images, vq_mse the mean squared error of out_vq_latent against gt_vq_latent.
+        Images with a side over SPLIT_DECODE_RESOLUTION are refused: the tiled decoder does not produce out_vq_latent."""
+        from . import metrics
+        from .train import kernels as K
+        beta_rate = float(beta_rate) if beta_rate is not None else self.max_beta_rate / 2.0
+        beta_vq = float(beta_vq) if beta_vq is not None else self.max_beta_vq / 2.0
+        rows = []
+        for idx, x in enumerate(list(images)[:max_sample_size]):
+            if x.dim() != 4 or x.shape[0] != 1:
+                raise ValueError(f"validation: image {idx} has shape {tuple(x.shape)}, expected [1, 3, H, W]")
+            if max(x.shape[2:]) > SPLIT_DECODE_RESOLUTION:
+                raise ValueError(f"validation: image {idx} is {x.shape[3]} x {x.shape[2]}; sides over {SPLIT_DECODE_RESOLUTION} decode "
+                                 "tiled, without the out_vq_latent that vq_mse needs")
+            out = self.run_model(x, is_train=False, beta_rate=beta_rate, beta_vq=beta_vq)
+            ms, psnr = metrics.ms_ssim_psnr(out["real_images"], out["fake_images"])
+            emb, gt = out["out_vq_latent"], out["gt_vq_latent"].contiguous()
+            vq_mse = K.reduce_loss(0, emb, gt, 1.0 / emb.numel())
+            rows.append(dict(idx=idx + 1, bpp=float(out["bpp"]), psnr=float(psnr[0]), ms_ssim=float(ms[0]), vq_acc=float(out["vq_accuracy"]),
+                             vq_mse=float(vq_mse[0])))
+        return rows
 
     # ------------------------------------------------------------------ compress (330-376)
     @torch.no_grad()

@@ -292,3 +292,40 @@ def lpips(model, x: Tensor, y: Tensor) -> Tensor:
     out = torch.empty(N, dtype=torch.float64, device=x.device)
     check(lib().dcvic_lpips_score_f64(_p(mom), N, taps, _p(out), _stream()), "lpips_score")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ MS-SSIM and PSNR
+MSSSIM_MIN_SIDE = 161          # pytorch-msssim 0.2.1 asserts min(H, W) > (win_size - 1) * 2**4
+
+
+def msssim_psnr_sse(x: Tensor, y: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """(ms_ssim [N], psnr [N], sse [N]) fp64 on the device for x, y contiguous fp32 [N, 3, H, W] in [-1, 1] (csrc/ssim.hip): the
+    reference's calc_ms_ssim (pytorch-msssim 0.2.1 on trunc((v + 1) / 2 * 255), -1 where min(H, W) <= 160, which the package refuses
+    and the reference reports as -1) and calc_psnr (10 log10(255^2 / mse) on the same integers; inf for identical images); sse is the
+    exact squared-error sum of the integer planes."""
+    N, Cc, H, W = _chk4(x, "ms_ssim x")
+    if tuple(y.shape) != tuple(x.shape):
+        raise ValueError(f"ms_ssim_psnr: x and y differ in shape {tuple(x.shape)} vs {tuple(y.shape)}")
+    _chk4(y, "ms_ssim y")
+    if Cc != 3:
+        raise ValueError(f"ms_ssim_psnr: need RGB images [N, 3, H, W], got {tuple(x.shape)}")
+    if not (x.is_contiguous() and y.is_contiguous()):
+        raise ValueError("ms_ssim_psnr: x and y must be contiguous")
+    if y.device != x.device:
+        raise ValueError(f"ms_ssim_psnr: x on {x.device}, y on {y.device}")
+    full = min(H, W) >= MSSSIM_MIN_SIDE
+    psnr = torch.empty(N, dtype=torch.float64, device=x.device)
+    sse = torch.empty(N, dtype=torch.float64, device=x.device)
+    ms = torch.empty(N, dtype=torch.float64, device=x.device) if full else torch.full((N,), -1.0, dtype=torch.float64, device=x.device)
+    nb = int(lib().dcvic_msssim_workspace_bytes(N, Cc, H, W))
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
+    check(lib().dcvic_msssim_psnr_f64(_p(x), _p(y), N, Cc, H, W, _p(ms) if full else None, _p(psnr), _p(sse), _p(ws), C.c_longlong(nb),
+                                      _stream()), "msssim_psnr")
+    return ms, psnr, sse
+
+
+@torch.no_grad()
+def ms_ssim_psnr(x: Tensor, y: Tensor) -> Tuple[Tensor, Tensor]:
+    """(ms_ssim [N], psnr [N]) fp64 on the device; see msssim_psnr_sse."""
+    ms, psnr, _ = msssim_psnr_sse(x, y)
+    return ms, psnr

@@ -172,6 +172,26 @@ class DualBetaCondGanDistortionVqCodeTrainer:
         self.g_group.refresh_plans(); self.d_group.refresh_plans()
         self._drop_inference_graphs()
 
+    # dual_cond_rate_distortion_vq_code_trainer.py:202-233 (_validation)
+    def validation_beta_pairs(self) -> List[Tuple[float, float, str]]:
+        """(beta_rate, beta_vq, label): the first selected pair when the model uses selected pairs, else the four corners."""
+        m = self.model
+        if getattr(m, "use_selected_beta_pairs", False):
+            return [(float(m.selected_beta_rate[0]), float(m.selected_beta_vq[0]), "idx0")]
+        br, bv = float(m.max_beta_rate), float(m.max_beta_vq)
+        return [(br, 0.0, "rate_max_vq_000"), (br, bv, "rate_max_vq_max"), (0.0, 0.0, "rate_000_vq_000"), (0.0, bv, "rate_000_vq_max")]
+
+    def validation(self, current_iter: int, images: List[Tensor]) -> Dict[str, float]:
+        """{<label>_<metric>: mean over `images`} for every validation beta pair, on the weights of `current_iter` (the packed plans
+        are refreshed by every optimizer step).  Runs the inference path only -- no graph capture, no draw from the beta sampler, no
+        touch of the optimizer, scheduler, discriminator or data state -- so training continues exactly as without it."""
+        out: Dict[str, float] = {}
+        for beta_rate, beta_vq, label in self.validation_beta_pairs():
+            rows = self.model.validation(images, max_sample_size=100, beta_rate=beta_rate, beta_vq=beta_vq)
+            for k in ("bpp", "psnr", "ms_ssim", "vq_acc", "vq_mse"):
+                out[f"{label}_{k}"] = sum(r[k] for r in rows) / len(rows)
+        return out
+
     # hyperprior_dc_vic_model.py:99-110
     def sample_selected_beta_pair(self, n: int) -> Tuple[Tensor, Tensor]:
         m = self.model

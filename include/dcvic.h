@@ -441,6 +441,20 @@ int dcvic_fid_pool3_f32(int mode, const float* x, long long x_bs, int N, int C, 
 int dcvic_fid_mean_hw_f32(const float* x, long long x_bs, int N, int C, int HW, float* y, long long y_bs, void* stream);
 int dcvic_fid_stats_accum_f64(const float* F, long long f_rs, int B, int D, double* sum, double* gram, void* stream);
 
+/* MS-SSIM and PSNR for the trainer's validation (the reference's calc_ms_ssim / calc_psnr on pytorch-msssim 0.2.1; csrc/ssim.hip; parity
+ * with the package unpinned -- it is not in the reference tree).  x, y: N images of C dense H x W fp32 planes in [-1, 1], both
+ * converted to trunc((v + 1) * 0.5 * 255) first.  Per image n:
+ *   ms_ssim[n]: 5-scale MS-SSIM (11-tap Gaussian sigma 1.5, valid filtering, K = (0.01, 0.03), data_range 255, weights
+ *               [0.0448, 0.2856, 0.3001, 0.2363, 0.1333], avg_pool2d(2, padding = size % 2) between scales), averaged over channels;
+ *               needs min(H, W) > 160 (an argument error otherwise, where the package asserts).  NULL: PSNR only, any H, W;
+ *   sse[n]:     the exact squared-error sum of the integer planes (an integer held in fp64);
+ *   psnr[n]:    10 log10(255^2 / (sse / (C H W))), inf for identical images.
+ * workspace: at least dcvic_msssim_workspace_bytes(N, C, H, W) bytes (256-byte aligned), C <= 64.  No allocation or synchronisation
+ * (graph-capturable); planes are launched in groups of at most 65535 (grid.y); every image's values are batch-invariant. */
+long long dcvic_msssim_workspace_bytes(int N, int C, int H, int W);
+int dcvic_msssim_psnr_f64(const float* x, const float* y, int N, int C, int H, int W, double* ms_ssim, double* psnr, double* sse,
+                          void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

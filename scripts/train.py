@@ -17,6 +17,10 @@ dict of lpips.LPIPS(net='alex'), loaded with weights_only=True); its weights can
 perceptual weight is an ERROR unless --allow_synthetic_lpips opts into synthetic AlexNet weights (benchmarks / plumbing only).
 --save_step also writes training_state_iter*.pth.tar (Adam moments, step counts, scheduler epochs, beta-sampler RNG; the
 reference saves optimizer + scheduler state too, base_trainer.py:178-214) and --resume continues from it.
+Validation (base_trainer.py:130-192): every --eval_step iterations (YAML `eval_step`, 0 = off) rank 0 runs the sorted *.png of
+--eval_dataset_root (YAML `dataset.eval_dataset.root_dir`; at most 100, decoded once at start-up) through the model and prints
+`validation iterN` with one `key: value` line per metric; with --save_dir the row {iter, <label>_<metric>...} is appended to
+<save_dir>/eval_result.csv (--resume carries the earlier rows over).  Its time is left out of samples/s.
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dc_vic_amd import BaseConfig, build_comp_model  # noqa: E402
 from dc_vic_amd.parallel import launched_by_a_launcher, pin_rank_cpus, self_launch  # noqa: E402
 from dc_vic_amd.train import DualBetaCondGanDistortionVqCodeTrainer, DualBetaCondTamingNLayerDiscriminator  # noqa: E402
+from dc_vic_amd.train.validation import EvalCSV, eval_image_paths, load_eval_images  # noqa: E402
 
 
 def _get(d, *keys, default=None):
@@ -99,13 +104,26 @@ def main():
     p.add_argument("--allow_synthetic_lpips", action="store_true", help="train the perceptual term against SYNTHETIC AlexNet / head weights (plumbing / benchmarks only)")
     p.add_argument("--resume", type=str, default=None, help="training_state_iterXXXXXXX.pth.tar written by --save_step (loads the comp_model / discriminator files beside it)")
     p.add_argument("--gpus", type=int, default=0, help="data-parallel over N GPUs of this node: without a launcher this process starts the N ranks itself")
+    p.add_argument("--eval_dataset_root", type=str, default=None, help="folder of eval PNGs (overrides the YAML's dataset.eval_dataset.root_dir)")
+    p.add_argument("-e", "--eval_step", type=int, default=None, help="validate every N iterations (overrides the YAML's eval_step; 0 = off)")
     a = p.parse_args()
+    if a.eval_dataset_root is not None:
+        try:                                          # a folder named on the command line must hold PNGs: checked before any GPU work
+            eval_image_paths(a.eval_dataset_root)
+        except ValueError as e:
+            raise SystemExit(f"--eval_dataset_root: {e}")
     if a.gpus > 1 and not launched_by_a_launcher():
         sys.exit(self_launch(a.gpus))                     # parent: never touches the GPU
     if a.gpus > 0 and int(os.environ.get("WORLD_SIZE", "1")) != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={os.environ.get('WORLD_SIZE', '1')}")
 
     rank, world, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
+    eval_images = None
+    if a.eval_dataset_root is not None and rank == 0:
+        try:
+            eval_images = load_eval_images(a.eval_dataset_root)
+        except ValueError as e:
+            raise SystemExit(f"--eval_dataset_root: {e}")
     pin_rank_cpus()
     dist = None
     device = a.device
@@ -168,6 +186,26 @@ def main():
         trainer.resync_parameters()
         start_iter = trainer.load_training_state(st)
     total_iter = a.total_iter or int(_get(opt, "total_iter", default=500000))
+    eval_step = a.eval_step if a.eval_step is not None else int(_get(opt, "eval_step", default=10000))
+    eval_root = a.eval_dataset_root or _get(opt, "dataset", "eval_dataset", "root_dir", default=None)
+    if a.eval_dataset_root is None and eval_root and eval_step > 0 and rank == 0:
+        if os.path.isdir(eval_root) and glob(os.path.join(eval_root, "*.png")):
+            eval_images = load_eval_images(eval_root)
+        else:
+            print(f'[train] eval_dataset.root_dir "{eval_root}" holds no PNG: training without validation', flush=True)
+    do_eval = bool(eval_root) and eval_step > 0 and (rank != 0 or eval_images is not None)
+    if world > 1:                                     # every rank must agree on whether to meet at the validation barrier
+        flag = torch.tensor([1 if do_eval else 0], device=device)
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+        do_eval = bool(flag.item())
+    eval_csv = None
+    if do_eval and rank == 0 and a.save_dir:
+        os.makedirs(a.save_dir, exist_ok=True)
+        path = os.path.join(a.save_dir, "eval_result.csv")
+        prev = None
+        if a.resume:                                  # base_trainer.py: the job's CSV is loaded and extended
+            prev = path if os.path.exists(path) else os.path.join(os.path.dirname(a.resume), "eval_result.csv")
+        eval_csv = EvalCSV(path, resume_from=prev, start_iter=start_iter)
     data = None if a.synthetic_data else CropDataset(a.dataset_root, 256, rank, world, a.seed)
     gen = torch.Generator().manual_seed(a.seed * 7919 + rank)
     if a.save_dir and rank == 0:
@@ -176,13 +214,26 @@ def main():
         for _ in range(start_iter):          # resume: the synthetic stream continues where the interrupted run stopped
             torch.rand((a.batch_size, 3, 256, 256), generator=gen)
     t0 = time.perf_counter()
+    t_eval = 0.0                                      # time spent in validation (and at its barrier): not training throughput
     for it in range(start_iter + 1, total_iter + 1):
         x = (torch.rand((a.batch_size, 3, 256, 256), generator=gen) * 2 - 1) if data is None else data.batch(a.batch_size)
         log = trainer.optimize_parameters(it, {"real_images": x})
         if rank == 0 and (it % a.log_step == 0 or it == 1 or it == total_iter):
-            dt = time.perf_counter() - t0
+            dt = time.perf_counter() - t0 - t_eval
             msg = "skipped (loss anomaly)" if log is None else " ".join(f"{k} {v:.5g}" for k, v in log.items())
             print(f"iter {it:7d} | {world * a.batch_size * (it - start_iter) / dt:7.2f} samples/s | {msg}", flush=True)
+        if do_eval and it % eval_step == 0:
+            tv = time.perf_counter()
+            if rank == 0:
+                res = trainer.validation(it, eval_images)
+                # base_trainer.py:178-192: the log lines, then the CSV row
+                print(f"validation iter{it} ({time.perf_counter() - tv:.2f} s)\n" + "".join(f"\t {k}: {v:.4f}\n" for k, v in res.items()),
+                      end="", flush=True)
+                if eval_csv is not None:
+                    eval_csv.append({"iter": it, **res})
+            if dist is not None:
+                dist.barrier()
+            t_eval += time.perf_counter() - tv
         if a.save_dir and a.save_step and it % a.save_step == 0 and rank == 0:
             torch.save({"iter": it, "comp_model": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}},
                        os.path.join(a.save_dir, f"comp_model_iter{it:07d}.pth.tar"))

@@ -74,6 +74,8 @@ SYMBOLS = [
     "dcvic_groupnorm_bwd_f32", "dcvic_layernorm_c_bwd_blocks", "dcvic_layernorm_c_bwd_f32", "dcvic_softmax_c_bwd_f32",
     "dcvic_swin_attn_bwd_f32", "dcvic_reduce_loss_f32", "dcvic_cross_entropy_f32", "dcvic_adam_step_f32", "dcvic_clip_scale_f32",
     "dcvic_resample2_f32", "dcvic_s2d_f32", "dcvic_maxpool3s2_f32", "dcvic_lpips_tap_f32",
+    # OASIS GAN loss (csrc/oasis.hip)
+    "dcvic_oasis_ce_workspace_doubles", "dcvic_oasis_ce_f32",
     # full-reference metrics (csrc/metrics.hip)
     "dcvic_l2pool_f32", "dcvic_pair_moments_workspace_doubles", "dcvic_pair_moments_f64", "dcvic_dists_score_f64", "dcvic_lpips_score_f64",
     # HiFiC patch FID (csrc/fid.hip)
@@ -107,6 +109,8 @@ def lib() -> C.CDLL:
     L.dcvic_wino44_ups_packed_bytes.restype = C.c_size_t
     L.dcvic_conv3x3_bf16_packed_bytes.restype = C.c_size_t
     L.dcvic_conv_wgrad_workspace_floats.restype = C.c_longlong
+    L.dcvic_oasis_ce_workspace_doubles.restype = C.c_longlong
+    L.dcvic_oasis_ce_workspace_doubles.argtypes = [C.c_int, C.c_int]
     L.dcvic_pair_moments_workspace_doubles.restype = C.c_longlong
     L.dcvic_pair_moments_workspace_doubles.argtypes = [C.c_longlong, C.c_longlong]
     L.dcvic_msssim_workspace_bytes.restype = C.c_longlong

@@ -468,3 +468,15 @@ def cross_entropy_loss(ctx: Ctx, logits: Var, target: Tensor, weight: float) -> 
     val = K.reduce_loss(3, nll, None, weight / m)
     acc(logits, dl)
     return val
+
+
+def oasis_gan_loss(ctx: Ctx, logits: Var, target: Tensor, is_real: bool, weight: float, want_score: bool = False):
+    """weight * CrossEntropy(logits [N, C, H, W], target + 1 if is_real else 0), mean over N*H*W (src/losses/oasis_gan_loss.py:40-79):
+    value, gradient and -- with want_score -- mean(logits[:, 1:]) from one pass of csrc/oasis.hip.  Returns the value, or
+    (value, score) with want_score; the gradient is seeded into `logits`."""
+    ld = _dense(logits.data)
+    N, Cc, H, W = ld.shape
+    val, dl, score = K.oasis_ce(ld, target.contiguous(), is_real, weight / (N * H * W), want_grad=logits.needs_grad, want_score=want_score)
+    if dl is not None:
+        acc(logits, dl)
+    return (val, score) if want_score else val

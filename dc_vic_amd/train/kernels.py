@@ -138,6 +138,27 @@ def cross_entropy(logits: Tensor, target: Tensor, w: float, want_grad: bool = Tr
     return nll, dl
 
 
+def oasis_ce(logits: Tensor, target: Optional[Tensor], is_real: bool, scale: float, want_grad: bool = True, want_score: bool = False):
+    """OASIS GAN loss (csrc/oasis.hip) in one pass over logits [N, C, H, W]: (loss, dlogits or None, score or None) with
+    loss = scale * sum_positions CE(logits, index + 1 if is_real else 0), dlogits its gradient and score = mean(logits[:, 1:])."""
+    if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("oasis_ce: contiguous fp32 logits [N, C, H, W]")
+    N, Cc, H, W = logits.shape
+    if target is not None and (target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != N * H * W):
+        raise ValueError(f"oasis_ce: contiguous int64 targets with {N * H * W} elements")
+    need = int(lib().dcvic_oasis_ce_workspace_doubles(N, H * W))
+    key = ("oasis_ws", str(logits.device))
+    ws = _WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _WS[key] = torch.empty(max(need, 1024), dtype=torch.float64, device=logits.device)
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    score = torch.empty(1, dtype=torch.float32, device=logits.device) if want_score else None
+    check(lib().dcvic_oasis_ce_f32(_p(logits), _p(target), 1 if is_real else 0, C.c_double(scale), _p(loss), _p(dl), _p(score), _p(ws),
+                                   N, Cc, H * W, _stream()), "oasis_ce")
+    return loss, dl, score
+
+
 def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, b1: float, b2: float, eps: float, step: int, gscale: Optional[Tensor]) -> None:
     check(lib().dcvic_adam_step_f32(_p(p), _p(g), _p(m), _p(v), C.c_longlong(p.numel()), C.c_float(lr), C.c_float(b1), C.c_float(b2),
                                     C.c_float(eps), step, _p(gscale), _stream()), "adam_step")

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..registry import LOSS_REGISTRY, TRAINER_REGISTRY
 from . import autograd as A
 from . import kernels as K
 from . import nets
@@ -94,6 +95,7 @@ class Adam:
         g.refresh_plans()
 
 
+@TRAINER_REGISTRY.register()
 class DualBetaCondGanDistortionVqCodeTrainer:
     def __init__(self, model, discriminator, lr_g: float = 1e-4, lr_d: float = 1e-4, milestones=(300000,), gamma: float = 0.1,
                  clip_max_norm: Optional[float] = 1.0, loss_weights: Optional[Dict[str, float]] = None, sample_beta_batch: bool = True,
@@ -228,10 +230,14 @@ class DualBetaCondGanDistortionVqCodeTrainer:
         else:
             log["perceptual"] = torch.zeros(1, device=self.device)
         g_fake = nets.discriminator_forward(ctx, self.D, o["fake"], beta_rate, beta_vq)
-        log["adv"] = A.bce_logits_loss(ctx, g_fake, True, w["gan"])
+        log["adv"] = self.calc_adv_loss(ctx, g_fake, o["gt_vq_indices"])
         log["code_distortion"] = A.mse_loss(ctx, o["pred_embed"], o["gt_vq_latent"], w["code_distortion"])
         log["code_ce"] = A.cross_entropy_loss(ctx, o["logits"], o["gt_vq_indices"], w["code_ce"])
         return log
+
+    def calc_adv_loss(self, ctx: Ctx, g_fake, gt_vq_indices: Tensor) -> Tensor:
+        """The generator's adversarial term: gan_loss(D(fake), is_real=True, is_disc=False) (:213-216)."""
+        return A.bce_logits_loss(ctx, g_fake, True, self.w["gan"])
 
     def optimize_parameters(self, current_iter: int, data_dict: Dict) -> Optional[Dict[str, float]]:
         real = data_dict["real_images"]
@@ -263,17 +269,92 @@ class DualBetaCondGanDistortionVqCodeTrainer:
         dctx = Ctx([self.d_group])
         fake_det = o["fake"].data                      # .detach()
         self.last_fake = fake_det
-        d_real = nets.discriminator_forward(dctx, self.D, A.const(o["real"]), beta_rate, beta_vq)
-        d_fake = nets.discriminator_forward(dctx, self.D, A.const(fake_det), beta_rate, beta_vq)
-        l_real = A.bce_logits_loss(dctx, d_real, True, 0.5)
-        l_fake = A.bce_logits_loss(dctx, d_fake, False, 0.5)
+        d_real, d_fake = self.run_discriminator(dctx, o["real"], fake_det, beta_rate, beta_vq)
+        l_real, l_fake = self.calc_d_loss(dctx, d_real, d_fake, o["gt_vq_indices"])
         dctx.backward()
         allreduce_mean_(self.d_group.grad, self.dist)
         self.d_opt.step(self.d_sched.lr())
         self.d_sched.step()
         vq_acc = float((o["out_vq_indices"] == o["gt_vq_indices"]).float().mean().item())
         log = {k: float(v.item()) for k, v in g_log.items()}
+        out_d_real, out_d_fake = self.calc_avg_d_score_for_log(d_real, d_fake)
         log.update(total=total, qbpp=o["qbpp"], vq_acc=vq_acc, lr=lr_now, d_real=float(l_real.item()), d_fake=float(l_fake.item()),
-                   d_total=float(l_real.item()) + float(l_fake.item()),
-                   out_d_real=float(d_real.data.mean().item()), out_d_fake=float(d_fake.data.mean().item()))
+                   d_total=float(l_real.item()) + float(l_fake.item()), out_d_real=out_d_real, out_d_fake=out_d_fake)
         return log
+
+    # :236-300 (run_discriminator, calc_d_loss, calc_avg_d_score_for_log): the hooks a subclass with another adversarial loss overrides
+    def run_discriminator(self, dctx: Ctx, real: Tensor, fake_det: Tensor, beta_rate, beta_vq):
+        d_real = nets.discriminator_forward(dctx, self.D, A.const(real), beta_rate, beta_vq)
+        d_fake = nets.discriminator_forward(dctx, self.D, A.const(fake_det), beta_rate, beta_vq)
+        return d_real, d_fake
+
+    def calc_d_loss(self, dctx: Ctx, d_real, d_fake, gt_vq_indices: Tensor):
+        """(0.5 * loss on real, 0.5 * loss on fake), each seeding its gradient on the tape."""
+        l_real = A.bce_logits_loss(dctx, d_real, True, 0.5)
+        l_fake = A.bce_logits_loss(dctx, d_fake, False, 0.5)
+        return l_real, l_fake
+
+    def calc_avg_d_score_for_log(self, d_real, d_fake) -> Tuple[float, float]:
+        return float(d_real.data.mean().item()), float(d_fake.data.mean().item())
+
+
+# ---------------------------------------------------------------------------------------------------- OASIS GAN loss / trainer
+def _verify_logit_target_shape(logits_shape, target: Tensor) -> None:
+    """src/losses/oasis_gan_loss.py:17-28, same messages."""
+    if len(logits_shape) != 4:
+        raise ValueError("Only expect 4-dimensional logits.")
+    expected_target_numel = logits_shape[0] * logits_shape[-2] * logits_shape[-1]
+    actual_target_shape = target.numel()
+    if expected_target_numel != actual_target_shape:
+        raise ValueError(f"Based on logits size {logits_shape}, expected target numel to be "
+                         f"{expected_target_numel}, but found {actual_target_shape}")
+
+
+@LOSS_REGISTRY.register()
+class OasisGANLoss:
+    """src/losses/oasis_gan_loss.py:31-79: the discriminator classifies every VQ token position into n_embed + 1 classes (0 = fake,
+    k + 1 = real with codebook entry k); every adversarial term is a cross entropy against the ground-truth indices.  `loss_weight`
+    multiplies the generator side only (is_disc=False).  `logits` is a `Var` (or a tensor): value, gradient and the optional log
+    score come from one launch of dcvic_oasis_ce_f32; `weight` is the trainer's extra factor (0.5 on the D side)."""
+
+    def __init__(self, loss_weight: float):
+        self.lamb_gan = float(loss_weight)
+
+    def __call__(self, ctx: Ctx, logits, target: Tensor, is_disc: bool, is_real: bool, weight: float = 1.0, want_score: bool = False):
+        lv = logits if isinstance(logits, A.Var) else A.const(logits)
+        _verify_logit_target_shape(lv.data.shape, target)
+        if target.dtype != torch.long:
+            raise ValueError("Expected target to have dtype torch.long.")
+        return A.oasis_gan_loss(ctx, lv, target, is_real, weight * (1.0 if is_disc else self.lamb_gan), want_score=want_score)
+
+
+@TRAINER_REGISTRY.register()
+class DualBetaCondOasisGanDistortionVqFusionTrainer(DualBetaCondGanDistortionVqCodeTrainer):
+    """src/trainer/dual_cond_oasis_gan_distortion_vq_code_trainer.py:16-113 (config/dc_vic_oasis.yaml): the stage-3 trainer with the
+    OASIS adversarial loss.  Overrides what the reference overrides -- the adversarial term of calc_g_loss, calc_d_loss and the
+    out_d_* log values (mean over the channels 1:) -- and inherits everything else.  `trainer.mc_sampling` (a D half of the batch
+    with dataset-supplied indices) is not built."""
+
+    def __init__(self, model, discriminator, *args, **kwargs):
+        n_embed = int(model.vq_model.quantize.embedding.weight.shape[0])
+        last = discriminator.main[-1]
+        if int(last.out_channels) != n_embed + 1:
+            raise ValueError(f"OASIS discriminator: out_nc is {int(last.out_channels)}, the model's codebook needs n_embed + 1 = {n_embed + 1} classes")
+        if int(last.kernel_size) != 3:
+            raise ValueError("OASIS discriminator: keep_shape must be True so that the logits map is the VQ token grid (H / 8 x W / 8)")
+        super().__init__(model, discriminator, *args, **kwargs)
+        self.gan_loss = OasisGANLoss(self.w["gan"])
+        self._d_scores: Optional[Tuple[Tensor, Tensor]] = None
+
+    def calc_adv_loss(self, ctx: Ctx, g_fake, gt_vq_indices: Tensor) -> Tensor:
+        return self.gan_loss(ctx, g_fake, gt_vq_indices, is_disc=False, is_real=True)
+
+    def calc_d_loss(self, dctx: Ctx, d_real, d_fake, gt_vq_indices: Tensor):
+        l_real, s_real = self.gan_loss(dctx, d_real, gt_vq_indices, is_disc=True, is_real=True, weight=0.5, want_score=True)
+        l_fake, s_fake = self.gan_loss(dctx, d_fake, gt_vq_indices, is_disc=True, is_real=False, weight=0.5, want_score=True)
+        self._d_scores = (s_real, s_fake)
+        return l_real, l_fake
+
+    def calc_avg_d_score_for_log(self, d_real, d_fake) -> Tuple[float, float]:
+        s_real, s_fake = self._d_scores
+        return float(s_real.item()), float(s_fake.item())

@@ -383,6 +383,16 @@ int dcvic_reduce_loss_f32(int kind, const float* a, const float* b, long long le
                           double* workspace, void* stream);
 /* Cross entropy over the channel axis (src/losses/cross_entropy_loss.py): per-pixel nll and dlogits = w * (softmax - onehot). */
 int dcvic_cross_entropy_f32(const float* logits, const int64_t* target, float* nll, float* dlogits, int N, int C, int HW, float w, void* stream);
+/* OASIS GAN loss (src/losses/oasis_gan_loss.py; csrc/oasis.hip) on logits [N][C][HW] (fp32, dense) and int64 VQ indices [N][HW]:
+ * the class per position is index + 1 when is_real, else 0 (target may be NULL then); needs C >= 2 and index + 1 < C (an index
+ * outside that range makes the loss NaN, it is never used as an address).
+ *   loss[0]  = scale * sum_positions (logsumexp_c - logit[class])      (fp64 sum in a fixed order; the caller passes weight / (N*HW))
+ *   dlogits  = scale * (softmax - onehot(class)), or NULL for the value only
+ *   score[0] = mean(logits[:, 1:, :]) (calc_avg_d_score_for_log of the OASIS trainer), or NULL
+ * workspace: dcvic_oasis_ce_workspace_doubles(N, HW) doubles (0 for an empty tensor).  Bitwise reproducible. */
+long long dcvic_oasis_ce_workspace_doubles(int N, int HW);
+int dcvic_oasis_ce_f32(const float* logits, const int64_t* target, int is_real, double scale, float* loss, float* dlogits, float* score,
+                       double* workspace, int N, int C, int HW, void* stream);
 /* torch.optim.Adam step on a flat parameter buffer; gscale (device scalar or NULL) multiplies the gradient first. */
 int dcvic_adam_step_f32(float* p, const float* g, float* m, float* v, long long len, float lr, float beta1, float beta2, float eps,
                         int step, const float* gscale, void* stream);

@@ -21,6 +21,9 @@ Validation (base_trainer.py:130-192): every --eval_step iterations (YAML `eval_s
 --eval_dataset_root (YAML `dataset.eval_dataset.root_dir`; at most 100, decoded once at start-up) through the model and prints
 `validation iterN` with one `key: value` line per metric; with --save_dir the row {iter, <label>_<metric>...} is appended to
 <save_dir>/eval_result.csv (--resume carries the earlier rows over).  Its time is left out of samples/s.
+GAN loss: `DualBetaCondGanDistortionVqCodeTrainer` (PatchGAN, VanillaGANLoss) or `DualBetaCondOasisGanDistortionVqFusionTrainer`
+(config/dc_vic_oasis.yaml: 257-way per-token discriminator, OasisGANLoss), chosen by --gan {vanilla,oasis}, else the YAML's
+`trainer.type`, else `loss.gan_loss.type`, else the discriminator's `out_nc` (1 -> vanilla, n_embed + 1 -> oasis); see choose_gan_trainer.
 """
 from __future__ import annotations
 
@@ -37,7 +40,8 @@ import torch
 sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dc_vic_amd import BaseConfig, build_comp_model  # noqa: E402
 from dc_vic_amd.parallel import launched_by_a_launcher, pin_rank_cpus, self_launch  # noqa: E402
-from dc_vic_amd.train import DualBetaCondGanDistortionVqCodeTrainer, DualBetaCondTamingNLayerDiscriminator  # noqa: E402
+from dc_vic_amd.registry import TRAINER_REGISTRY  # noqa: E402
+from dc_vic_amd.train import DualBetaCondTamingNLayerDiscriminator  # noqa: E402  (registers both stage-3 trainers)
 from dc_vic_amd.train.validation import EvalCSV, eval_image_paths, load_eval_images  # noqa: E402
 
 
@@ -48,6 +52,57 @@ def _get(d, *keys, default=None):
         except (KeyError, TypeError):
             return default
     return d
+
+
+VANILLA_TRAINER, OASIS_TRAINER = "DualBetaCondGanDistortionVqCodeTrainer", "DualBetaCondOasisGanDistortionVqFusionTrainer"
+_TRAINER_KIND = {VANILLA_TRAINER: "vanilla", OASIS_TRAINER: "oasis"}
+_LOSS_KIND = {"VanillaGANLoss": "vanilla", "OasisGANLoss": "oasis"}
+
+
+def choose_gan_trainer(opt, gan_flag=None):
+    """(kind, trainer class name, reason) for a parsed config (pure: no GPU, no model).  Order: the --gan flag; `trainer.type`;
+    `loss.gan_loss.type`; the discriminator's `out_nc` (absent or 1 -> vanilla, n_embed + 1 -> oasis).  SystemExit for an unknown
+    type, for `trainer.mc_sampling` (not built) and for a choice the discriminator cannot serve: OASIS needs out_nc = n_embed + 1
+    of the VQ codebook and keep_shape (one 257-way classification per token), the BCE PatchGAN must not get that discriminator."""
+    n_embed = _get(opt, "subnet", "vq_model", "n_embed")
+    out_nc = int(_get(opt, "discriminator", "out_nc", default=1))
+    keep_shape = bool(_get(opt, "discriminator", "keep_shape", default=False))
+    if _get(opt, "trainer", "mc_sampling", default=False):
+        raise SystemExit("trainer.mc_sampling: true is not built (the reference's split of a batch into a generator half and a discriminator "
+                         "half with dataset-supplied VQ indices): set it to false")
+    t_type, l_type = _get(opt, "trainer", "type"), _get(opt, "loss", "gan_loss", "type")
+    if gan_flag is not None:
+        if gan_flag not in ("vanilla", "oasis"):
+            raise SystemExit(f"--gan {gan_flag}: unknown, expected vanilla or oasis")
+        kind, reason = gan_flag, f"--gan {gan_flag}"
+    elif t_type is not None:
+        if t_type not in _TRAINER_KIND:
+            raise SystemExit(f"trainer.type: {t_type} is unknown, expected {VANILLA_TRAINER} or {OASIS_TRAINER}")
+        kind, reason = _TRAINER_KIND[t_type], f"trainer.type: {t_type}"
+    elif l_type is not None:
+        if l_type not in _LOSS_KIND:
+            raise SystemExit(f"loss.gan_loss.type: {l_type} is unknown, expected VanillaGANLoss or OasisGANLoss")
+        kind, reason = _LOSS_KIND[l_type], f"loss.gan_loss.type: {l_type}"
+    elif out_nc == 1:
+        kind, reason = "vanilla", "discriminator.out_nc: 1"
+    elif n_embed is not None and out_nc == int(n_embed) + 1:
+        kind, reason = "oasis", f"discriminator.out_nc: {out_nc} = n_embed + 1"
+    else:
+        raise SystemExit(f"discriminator.out_nc: {out_nc} names no GAN loss (1 -> vanilla, n_embed + 1 = "
+                         f"{'?' if n_embed is None else int(n_embed) + 1} -> oasis) and neither --gan, trainer.type nor loss.gan_loss.type is given")
+    if gan_flag is None and t_type in _TRAINER_KIND and l_type in _LOSS_KIND and _TRAINER_KIND[t_type] != _LOSS_KIND[l_type]:
+        raise SystemExit(f"trainer.type: {t_type} cannot train with loss.gan_loss.type: {l_type}")
+    if kind == "oasis":
+        if n_embed is None:
+            raise SystemExit(f"OASIS GAN loss ({reason}) needs subnet.vq_model.n_embed to size the discriminator's classes")
+        if out_nc != int(n_embed) + 1:
+            raise SystemExit(f"OASIS GAN loss ({reason}) cannot train a discriminator with out_nc: {out_nc}; it needs n_embed + 1 = {int(n_embed) + 1}")
+        if not keep_shape:
+            raise SystemExit(f"OASIS GAN loss ({reason}) cannot train a discriminator with keep_shape: false; its logits must lie on the VQ token grid")
+    elif n_embed is not None and out_nc == int(n_embed) + 1 and out_nc != 1:
+        raise SystemExit(f"vanilla GAN loss ({reason}) cannot train a discriminator with out_nc: {out_nc} (n_embed + 1 classes: an OASIS "
+                         "discriminator); use --gan oasis or out_nc: 1")
+    return kind, (OASIS_TRAINER if kind == "oasis" else VANILLA_TRAINER), reason
 
 
 class CropDataset:
@@ -106,7 +161,9 @@ def main():
     p.add_argument("--gpus", type=int, default=0, help="data-parallel over N GPUs of this node: without a launcher this process starts the N ranks itself")
     p.add_argument("--eval_dataset_root", type=str, default=None, help="folder of eval PNGs (overrides the YAML's dataset.eval_dataset.root_dir)")
     p.add_argument("-e", "--eval_step", type=int, default=None, help="validate every N iterations (overrides the YAML's eval_step; 0 = off)")
+    p.add_argument("--gan", choices=("vanilla", "oasis"), default=None, help="GAN loss / trainer (default: from the YAML, see choose_gan_trainer)")
     a = p.parse_args()
+    gan_kind, trainer_name, gan_reason = choose_gan_trainer(BaseConfig.fromfile(a.config_path, {"is_train": True}), a.gan)   # before any GPU work
     if a.eval_dataset_root is not None:
         try:                                          # a folder named on the command line must hold PNGs: checked before any GPU work
             eval_image_paths(a.eval_dataset_root)
@@ -168,7 +225,11 @@ def main():
             raise SystemExit(msg + "  Pass --lpips_path STATE_DICT, set loss.perceptual_loss.loss_weight: 0, or opt in with --allow_synthetic_lpips.")
         if rank == 0:
             print("[train] WARNING: " + msg, file=sys.stderr, flush=True)
-    trainer = DualBetaCondGanDistortionVqCodeTrainer(
+    if rank == 0:
+        w_src = "loss.gan_loss.loss_weight" if "gan" in lw else "default, no reference YAML pins it" if gan_kind == "oasis" else "default"
+        print(f"[train] GAN trainer: {gan_kind} ({trainer_name}), chosen by {gan_reason}; generator-side gan weight "
+              f"{lw.get('gan', DEFAULT_LOSS['gan']):g} ({w_src})", flush=True)
+    trainer = TRAINER_REGISTRY.get(trainer_name)(
         model, D, lr_g=float(_get(opt, "optim", "g_optimizer", "lr", default=1e-4)), lr_d=float(_get(opt, "optim", "d_optimizer", "lr", default=1e-4)),
         milestones=list(_get(opt, "optim", "g_scheduler", "milestones", default=[300000])), gamma=float(_get(opt, "optim", "g_scheduler", "gamma", default=0.1)),
         clip_max_norm=_get(opt, "optim", "clip_max_norm", default=1.0), loss_weights=lw,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """samples/s of the stage-3 training step (BASELINE config 5: 256x256 crops, batch 8 per GPU, G + D step) -- a SEPARATE metric,
-never mixed into bench.py's headline.  python tools/train_bench.py [--batch 8] [--steps 5] [--warmup 2]; under
+never mixed into bench.py's headline.  python tools/train_bench.py [--gan {vanilla,oasis}] [--batch 8] [--steps 5] [--warmup 2]
+(--gan oasis: the 257-class per-token discriminator of config/dc_vic_oasis.yaml and the OASIS cross-entropy loss); under
 torch.distributed.run it is data-parallel (weak scaling) and reports the aggregate."""
 import argparse
 import json
@@ -19,6 +20,7 @@ def main():
     p.add_argument("--batch", type=int, default=8)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--gan", choices=("vanilla", "oasis"), default="vanilla")
     a = p.parse_args()
     rank, world, lr_ = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(lr_)
@@ -31,12 +33,15 @@ def main():
         dist = dist_
     from dc_vic_amd import BaseConfig, build_comp_model
     from dc_vic_amd.synth import load_synth_weights
-    from dc_vic_amd.train import DualBetaCondGanDistortionVqCodeTrainer, DualBetaCondTamingNLayerDiscriminator
+    from dc_vic_amd.train import (DualBetaCondGanDistortionVqCodeTrainer, DualBetaCondOasisGanDistortionVqFusionTrainer,
+                                  DualBetaCondTamingNLayerDiscriminator)
     m = build_comp_model(BaseConfig.fromfile(os.path.join(ROOT, "config", "dc_vic_synthetic.yaml"), {"device": dev}))
     load_synth_weights(m, 1234)
     torch.manual_seed(0)
-    D = DualBetaCondTamingNLayerDiscriminator(input_nc=11, n_layers=3, ndf=64, norm_type="none", max_beta_1=3.0, max_beta_2=3.5).to(dev)
-    tr = DualBetaCondGanDistortionVqCodeTrainer(m, D, dist=dist, seed=rank)
+    dkw = dict(out_nc=m.vq_model.quantize.embedding.weight.shape[0] + 1, keep_shape=True) if a.gan == "oasis" else {}
+    D = DualBetaCondTamingNLayerDiscriminator(input_nc=11, n_layers=3, ndf=64, norm_type="none", max_beta_1=3.0, max_beta_2=3.5, **dkw).to(dev)
+    cls = DualBetaCondOasisGanDistortionVqFusionTrainer if a.gan == "oasis" else DualBetaCondGanDistortionVqCodeTrainer
+    tr = cls(m, D, dist=dist, seed=rank)
     g = torch.Generator().manual_seed(100 + rank)
     x = torch.rand((a.batch, 3, 256, 256), generator=g) * 2 - 1
     for _ in range(a.warmup):
@@ -53,7 +58,7 @@ def main():
     dt = time.perf_counter() - t0
     if rank == 0:
         print(json.dumps({"metric": "training samples/sec, stage-3 G+D step @256x256", "value": world * a.batch * a.steps / dt, "unit": "samples/s",
-                          "n_gpus": world, "steps": a.steps, "ms_per_step": 1e3 * dt / a.steps, "batch_per_gpu": a.batch, "dtype": "f32",
+                          "gan": a.gan, "n_gpus": world, "steps": a.steps, "ms_per_step": 1e3 * dt / a.steps, "batch_per_gpu": a.batch, "dtype": "f32",
                           "data": "synthetic", "lpips": "included, synthetic weights (parity unpinned)", "last_log": log}), flush=True)
     if dist is not None:
         dist.destroy_process_group()

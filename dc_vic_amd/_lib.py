@@ -52,37 +52,53 @@ class GemmArgs(C.Structure):
     ]
 
 
-# every symbol include/dcvic.h declares (tests/test_cabi.py checks the library exports all of them)
-SYMBOLS = [
-    "dcvic_last_error", "dcvic_version", "dcvic_device_info",
-    "dcvic_conv_desc_init", "dcvic_convT_phase_desc", "dcvic_conv_select_class", "dcvic_conv_last_variant", "dcvic_conv_set_tuning", "dcvic_conv_packed_bytes", "dcvic_conv_pack_f32", "dcvic_conv2d_f32",
-    "dcvic_wino_packed_bytes", "dcvic_wino_pack_f32", "dcvic_conv3x3_wino_f32",
-    "dcvic_wino_ups_packed_bytes", "dcvic_wino_ups_pack_f32", "dcvic_conv3x3_wino_ups_f32",
-    "dcvic_wino44_packed_bytes", "dcvic_wino44_pack_f32", "dcvic_conv3x3_wino44_f32",
-    "dcvic_conv3x3_thin_applies", "dcvic_conv3x3_thin_f32",
-    "dcvic_wino44_stats_tiles", "dcvic_conv3x3_wino44_stats_f32", "dcvic_groupnorm_part_f32",
-    "dcvic_wino44_ups_packed_bytes", "dcvic_wino44_ups_pack_f32", "dcvic_conv3x3_wino44_ups_f32", "dcvic_conv3x3_wino44_ups_stats_f32",
-    "dcvic_conv3x3_bf16_packed_bytes", "dcvic_conv3x3_bf16_mfma_shape", "dcvic_conv3x3_bf16_pack_f32", "dcvic_conv3x3_bf16_f32",
-    "dcvic_bgemm_f32", "dcvic_attn_fused_f32", "dcvic_groupnorm_f32", "dcvic_layernorm_c_f32", "dcvic_softmax_c_f32", "dcvic_swin_attn_f32",
-    "dcvic_ew_f32", "dcvic_chan_affine_f32", "dcvic_copy_planes_f32", "dcvic_copy_window_f32", "dcvic_absmax_f32", "dcvic_crop_clamp_f32",
-    "dcvic_vq_argmin_f32", "dcvic_argmax_lut_f32", "dcvic_gaussian_rate_f32", "dcvic_rate_blocks", "dcvic_neglog2_sum_f32", "dcvic_eb_rate_f32",
-    "dcvic_pmf_to_quantized_cdf_host", "dcvic_tables_create_host", "dcvic_tables_destroy_host",
-    "dcvic_rans_encode_batch_host", "dcvic_rans_decoder_create_host", "dcvic_rans_decoder_destroy_host",
-    "dcvic_rans_decode_batch_host",
+# The C ABI, stated once: every function include/dcvic.h declares as "return:parameters" type codes.  Every pointer parameter (structs
+# and the `void* stream` included) is a c_void_p, which takes byref(struct), an int address or None; s = const char* and v = void are
+# return types only.  lib() applies the table; tests/test_cabi.py holds it to the header's prototypes type for type.
+_CTYPE = {"i": C.c_int, "q": C.c_longlong, "f": C.c_float, "d": C.c_double, "z": C.c_size_t, "p": C.c_void_p, "s": C.c_char_p, "v": None}
+SIGNATURES = {
+    "dcvic_last_error": "s:", "dcvic_version": "i:", "dcvic_device_info": "i:pp",
+    "dcvic_conv_desc_init": "i:piiiiiiii", "dcvic_convT_phase_desc": "i:piiiii", "dcvic_conv_select_class": "i:piii", "dcvic_conv_last_variant": "i:",
+    "dcvic_conv_set_tuning": "i:iii", "dcvic_conv_packed_bytes": "z:p", "dcvic_conv_pack_f32": "i:pppp", "dcvic_conv2d_f32": "i:pppp",
+    "dcvic_wino_packed_bytes": "z:ii", "dcvic_wino_pack_f32": "i:ppiip", "dcvic_conv3x3_wino_f32": "i:iippp",
+    "dcvic_wino_ups_packed_bytes": "z:ii", "dcvic_wino_ups_pack_f32": "i:ppiip", "dcvic_conv3x3_wino_ups_f32": "i:iippp",
+    "dcvic_wino44_packed_bytes": "z:ii", "dcvic_wino44_pack_f32": "i:ppiip", "dcvic_conv3x3_wino44_f32": "i:iippp",
+    "dcvic_conv3x3_thin_applies": "i:ii", "dcvic_conv3x3_thin_f32": "i:piipp",
+    "dcvic_wino44_stats_tiles": "i:ii", "dcvic_conv3x3_wino44_stats_f32": "i:iipppp", "dcvic_groupnorm_part_f32": "i:pqpqppiiiifipip",
+    "dcvic_wino44_ups_packed_bytes": "z:ii", "dcvic_wino44_ups_pack_f32": "i:ppiip", "dcvic_conv3x3_wino44_ups_f32": "i:iippp",
+    "dcvic_conv3x3_wino44_ups_stats_f32": "i:iipppp",
+    "dcvic_conv3x3_bf16_packed_bytes": "z:ii", "dcvic_conv3x3_bf16_mfma_shape": "i:", "dcvic_conv3x3_bf16_pack_f32": "i:ppiip",
+    "dcvic_conv3x3_bf16_f32": "i:iiippp",
+    "dcvic_bgemm_f32": "i:pp", "dcvic_attn_fused_f32": "i:pppqpqiiifip", "dcvic_groupnorm_f32": "i:pqpqppiiiifip",
+    "dcvic_layernorm_c_f32": "i:ppppiiifp", "dcvic_softmax_c_f32": "i:piiip", "dcvic_swin_attn_f32": "i:pppiiiiiiip",
+    "dcvic_ew_f32": "i:ipqpqpqpqiiifip", "dcvic_chan_affine_f32": "i:pqpqppqpqiiip", "dcvic_copy_planes_f32": "i:pqiipqiiiiiiip",
+    "dcvic_copy_window_f32": "i:pqqqpqqqiiiip", "dcvic_absmax_f32": "i:pqpiqp", "dcvic_crop_clamp_f32": "i:pqiippiiiip",
+    "dcvic_vq_argmin_f32": "i:pppppiiiip", "dcvic_argmax_lut_f32": "i:ppppppiiiip", "dcvic_gaussian_rate_f32": "i:pqpppqpipqppqpppiiip",
+    "dcvic_rate_blocks": "i:q", "dcvic_neglog2_sum_f32": "i:pqppiqp", "dcvic_eb_rate_f32": "i:ppppppppppiiip",
+    "dcvic_pmf_to_quantized_cdf_host": "i:pip", "dcvic_tables_create_host": "p:piipp", "dcvic_tables_destroy_host": "v:p",
+    "dcvic_rans_encode_batch_host": "i:pppiqpqpi", "dcvic_rans_decoder_create_host": "p:pq", "dcvic_rans_decoder_destroy_host": "v:p",
+    "dcvic_rans_decode_batch_host": "i:pppiqpi",
     # training step (csrc/train.hip)
-    "dcvic_conv_wgrad_workspace_floats", "dcvic_conv_wgrad_f32", "dcvic_chan_reduce_f32", "dcvic_sum_rows_f32", "dcvic_ew_bwd_f32",
-    "dcvic_groupnorm_bwd_f32", "dcvic_layernorm_c_bwd_blocks", "dcvic_layernorm_c_bwd_f32", "dcvic_softmax_c_bwd_f32",
-    "dcvic_swin_attn_bwd_f32", "dcvic_reduce_loss_f32", "dcvic_cross_entropy_f32", "dcvic_adam_step_f32", "dcvic_clip_scale_f32",
-    "dcvic_resample2_f32", "dcvic_s2d_f32", "dcvic_maxpool3s2_f32", "dcvic_lpips_tap_f32",
+    "dcvic_conv_wgrad_workspace_floats": "q:iiiiiip", "dcvic_conv_wgrad_f32": "i:pqiiipqiiiiiiiiipipp", "dcvic_chan_reduce_f32": "i:pqpqpiiip",
+    "dcvic_sum_rows_f32": "i:ppiqip", "dcvic_ew_bwd_f32": "i:ippppqfiiiqp",
+    "dcvic_groupnorm_bwd_f32": "i:pqpqpqppppiiiifip", "dcvic_layernorm_c_bwd_blocks": "i:ii", "dcvic_layernorm_c_bwd_f32": "i:pppppiiifp",
+    "dcvic_softmax_c_bwd_f32": "i:pppiiifp",
+    "dcvic_swin_attn_bwd_f32": "i:ppppppiiiiiiiip", "dcvic_reduce_loss_f32": "i:ippqidppp", "dcvic_cross_entropy_f32": "i:ppppiiifp",
+    "dcvic_adam_step_f32": "i:ppppqffffipp", "dcvic_clip_scale_f32": "i:pfpp",
+    "dcvic_resample2_f32": "i:ippqiip", "dcvic_s2d_f32": "i:ppqiiiiiiip", "dcvic_maxpool3s2_f32": "i:pppppqiip",
+    "dcvic_lpips_tap_f32": "i:pppppiiifp",
     # OASIS GAN loss (csrc/oasis.hip)
-    "dcvic_oasis_ce_workspace_doubles", "dcvic_oasis_ce_f32",
+    "dcvic_oasis_ce_workspace_doubles": "q:ii", "dcvic_oasis_ce_f32": "i:ppidppppiiip",
     # full-reference metrics (csrc/metrics.hip)
-    "dcvic_l2pool_f32", "dcvic_pair_moments_workspace_doubles", "dcvic_pair_moments_f64", "dcvic_dists_score_f64", "dcvic_lpips_score_f64",
+    "dcvic_l2pool_f32": "i:ppqiip", "dcvic_pair_moments_workspace_doubles": "q:qq", "dcvic_pair_moments_f64": "i:ppiiqpqpp",
+    "dcvic_dists_score_f64": "i:pqppiipp", "dcvic_lpips_score_f64": "i:piipp",
     # HiFiC patch FID (csrc/fid.hip)
-    "dcvic_fid_patch_resize_f32", "dcvic_fid_pool3_f32", "dcvic_fid_mean_hw_f32", "dcvic_fid_stats_accum_f64",
+    "dcvic_fid_patch_resize_f32": "i:piipiiiipqp", "dcvic_fid_pool3_f32": "i:ipqiiiipqp", "dcvic_fid_mean_hw_f32": "i:pqiiipqp",
+    "dcvic_fid_stats_accum_f64": "i:pqiippp",
     # MS-SSIM and PSNR (csrc/ssim.hip)
-    "dcvic_msssim_workspace_bytes", "dcvic_msssim_psnr_f64",
-]
+    "dcvic_msssim_workspace_bytes": "q:iiii", "dcvic_msssim_psnr_f64": "i:ppiiiippppqp",
+}
+SYMBOLS = list(SIGNATURES)
 
 _lib = None
 
@@ -101,25 +117,10 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python dc_vic_amd/csrc/build.py` "
             "(or __graft_entry__.build()). dc_vic_amd has no fallback path.")
     L = C.CDLL(LIB_PATH)
-    L.dcvic_last_error.restype = C.c_char_p
-    L.dcvic_conv_packed_bytes.restype = C.c_size_t
-    L.dcvic_wino_packed_bytes.restype = C.c_size_t
-    L.dcvic_wino_ups_packed_bytes.restype = C.c_size_t
-    L.dcvic_wino44_packed_bytes.restype = C.c_size_t
-    L.dcvic_wino44_ups_packed_bytes.restype = C.c_size_t
-    L.dcvic_conv3x3_bf16_packed_bytes.restype = C.c_size_t
-    L.dcvic_conv_wgrad_workspace_floats.restype = C.c_longlong
-    L.dcvic_oasis_ce_workspace_doubles.restype = C.c_longlong
-    L.dcvic_oasis_ce_workspace_doubles.argtypes = [C.c_int, C.c_int]
-    L.dcvic_pair_moments_workspace_doubles.restype = C.c_longlong
-    L.dcvic_pair_moments_workspace_doubles.argtypes = [C.c_longlong, C.c_longlong]
-    L.dcvic_msssim_workspace_bytes.restype = C.c_longlong
-    L.dcvic_msssim_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-    L.dcvic_tables_create_host.restype = C.c_void_p
-    L.dcvic_rans_decoder_create_host.restype = C.c_void_p
-    L.dcvic_tables_destroy_host.argtypes = [C.c_void_p]
-    L.dcvic_rans_decoder_destroy_host.argtypes = [C.c_void_p]
-    L.dcvic_conv_packed_bytes.argtypes = [C.POINTER(ConvDesc)]
+    for name, sig in SIGNATURES.items():     # the package's only restype / argtypes assignments; other symbols stay untyped
+        fn = getattr(L, name)                # AttributeError names a symbol the library lacks
+        ret, params = sig.split(":")
+        fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[c] for c in params]
     _lib = L
     return L
 

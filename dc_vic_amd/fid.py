@@ -14,7 +14,6 @@ and F^T F) accumulate in fp64 on the device (dcvic_fid_stats_accum_f64), so feat
 bits whichever patches share its batch.  The Frechet distance is pytorch-fid's calculate_frechet_distance (scipy, fp64, host)."""
 from __future__ import annotations
 
-import ctypes as C
 from collections import OrderedDict
 from typing import Dict, Iterable, Optional, Tuple
 
@@ -343,7 +342,7 @@ def pool3(x: Tensor, mode: int, out: Optional[Tensor] = None) -> Tensor:
         out = _new(N, Cc, Ho, Wo, x)
     if tuple(_chk4(out, "fid pool out")) != (N, Cc, Ho, Wo):
         raise ValueError(f"fid pool: out shape {tuple(out.shape)} != {(N, Cc, Ho, Wo)}")
-    check(lib().dcvic_fid_pool3_f32(mode, _p(x), C.c_longlong(_bs(x)), N, Cc, H, W, _p(out), C.c_longlong(_bs(out)), _stream()), "fid_pool3")
+    check(lib().dcvic_fid_pool3_f32(mode, _p(x), _bs(x), N, Cc, H, W, _p(out), _bs(out), _stream()), "fid_pool3")
     return out
 
 
@@ -355,7 +354,7 @@ def mean_hw(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     if out.dtype != torch.float32 or out.device != x.device or tuple(out.shape) != (N, Cc) or (Cc > 1 and out.stride(1) != 1):
         raise ValueError(f"fid mean: out must be an fp32 [{N}, {Cc}] view with unit column stride on {x.device}")
     ys = out.stride(0) if N > 1 else Cc
-    check(lib().dcvic_fid_mean_hw_f32(_p(x), C.c_longlong(_bs(x)), N, Cc, H * W, _p(out), C.c_longlong(ys), _stream()), "fid_mean_hw")
+    check(lib().dcvic_fid_mean_hw_f32(_p(x), _bs(x), N, Cc, H * W, _p(out), ys, _stream()), "fid_mean_hw")
     return out
 
 
@@ -376,8 +375,7 @@ def patch_inputs(img: Tensor, origins: Tensor, ph: int, pw: Optional[int] = None
         out = torch.empty((B, 3, size, size), dtype=torch.float32, device=img.device)
     if tuple(_chk4(out, "fid patch out")) != (B, 3, size, size):
         raise ValueError(f"fid patch_inputs: out shape {tuple(out.shape)} != {(B, 3, size, size)}")
-    check(lib().dcvic_fid_patch_resize_f32(_p(img), H, W, _p(origins), B, ph, pw, size, _p(out), C.c_longlong(_bs(out)), _stream()),
-          "fid_patch_resize")
+    check(lib().dcvic_fid_patch_resize_f32(_p(img), H, W, _p(origins), B, ph, pw, size, _p(out), _bs(out), _stream()), "fid_patch_resize")
     return out
 
 
@@ -406,7 +404,7 @@ class FIDStats:
         B = feats.shape[0]
         if B == 0:
             return
-        check(lib().dcvic_fid_stats_accum_f64(_p(feats), C.c_longlong(feats.stride(0) if B > 1 else self.dims), B, self.dims, _p(self.sum),
+        check(lib().dcvic_fid_stats_accum_f64(_p(feats), feats.stride(0) if B > 1 else self.dims, B, self.dims, _p(self.sum),
                                               _p(self.gram), _stream()), "fid_stats_accum")
         self.n += B
 

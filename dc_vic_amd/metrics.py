@@ -14,7 +14,6 @@ x and y run through the network as ONE batch of 2N images.  The conv, pool and m
 value has the same bits whichever images share its batch.  No torch compute op touches the data: torch allocates and takes views."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -209,7 +208,7 @@ def l2pool(x: Tensor) -> Tensor:
     if not x.is_contiguous():
         raise ValueError("l2pool: x must be contiguous")
     y = torch.empty((N, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-    check(lib().dcvic_l2pool_f32(_p(x), _p(y), C.c_longlong(N * Cc), H, W, _stream()), "l2pool")
+    check(lib().dcvic_l2pool_f32(_p(x), _p(y), N * Cc, H, W, _stream()), "l2pool")
     return y
 
 
@@ -230,8 +229,7 @@ def pair_moments(f0: Tensor, f1: Tensor, out: Optional[Tensor] = None) -> Tensor
         raise ValueError("pair_moments: out must be an fp64 [N, C, 5] view with unit strides inside each image")
     ws = torch.empty(max(1, lib().dcvic_pair_moments_workspace_doubles(N * Cc, H * W)), dtype=torch.float64, device=f0.device)
     out_bs = out.stride(0) if N > 1 else max(out.stride(0), 5 * Cc)
-    check(lib().dcvic_pair_moments_f64(_p(f0), _p(f1), N, Cc, C.c_longlong(H * W), _p(out), C.c_longlong(out_bs), _p(ws), _stream()),
-          "pair_moments")
+    check(lib().dcvic_pair_moments_f64(_p(f0), _p(f1), N, Cc, H * W, _p(out), out_bs, _p(ws), _stream()), "pair_moments")
     return out
 
 
@@ -267,7 +265,7 @@ def dists(model: DISTSVGG, x: Tensor, y: Tensor) -> Tensor:
         pair_moments(h[:N], h[N:], out=mom[:, off:off + cs])
         off += cs
     out = torch.empty(N, dtype=torch.float64, device=x.device)
-    check(lib().dcvic_dists_score_f64(_p(mom), C.c_longlong(mom.stride(0)), _p(alpha), _p(beta), N, off, _p(out), _stream()), "dists_score")
+    check(lib().dcvic_dists_score_f64(_p(mom), mom.stride(0), _p(alpha), _p(beta), N, off, _p(out), _stream()), "dists_score")
     return out
 
 
@@ -287,7 +285,7 @@ def lpips(model, x: Tensor, y: Tensor) -> Tensor:
         w = getattr(model, f"lin{k}").model[1].weight.detach().reshape(-1).contiguous()
         pix = torch.empty((N, 1, H, W), dtype=torch.float32, device=x.device)
         f = f if f.is_contiguous() else A._dense(f)
-        check(lib().dcvic_lpips_tap_f32(_p(f[:N]), _p(f[N:]), _p(w), _p(pix), None, N, Cc, H * W, C.c_float(0.0), _stream()), "lpips_tap")
+        check(lib().dcvic_lpips_tap_f32(_p(f[:N]), _p(f[N:]), _p(w), _p(pix), None, N, Cc, H * W, 0.0, _stream()), "lpips_tap")
         pair_moments(pix, pix, out=mom[:, k:k + 1])           # spatial mean = mu_x of the map with itself (read once)
     out = torch.empty(N, dtype=torch.float64, device=x.device)
     check(lib().dcvic_lpips_score_f64(_p(mom), N, taps, _p(out), _stream()), "lpips_score")
@@ -319,7 +317,7 @@ def msssim_psnr_sse(x: Tensor, y: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     ms = torch.empty(N, dtype=torch.float64, device=x.device) if full else torch.full((N,), -1.0, dtype=torch.float64, device=x.device)
     nb = int(lib().dcvic_msssim_workspace_bytes(N, Cc, H, W))
     ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
-    check(lib().dcvic_msssim_psnr_f64(_p(x), _p(y), N, Cc, H, W, _p(ms) if full else None, _p(psnr), _p(sse), _p(ws), C.c_longlong(nb),
+    check(lib().dcvic_msssim_psnr_f64(_p(x), _p(y), N, Cc, H, W, _p(ms) if full else None, _p(psnr), _p(sse), _p(ws), nb,
                                       _stream()), "msssim_psnr")
     return ms, psnr, sse
 

@@ -17,8 +17,8 @@ from ._lib import (ACT_GELU, ACT_HALF_TANH, ACT_LRELU02, ACT_NONE, ACT_RELU, ACT
 Tensor = torch.Tensor
 
 
-def _stream() -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _chk4(t: Tensor, name: str = "tensor") -> Tuple[int, int, int, int]:
@@ -36,7 +36,10 @@ def _chk4(t: Tensor, name: str = "tensor") -> Tuple[int, int, int, int]:
     return N, Cc, H, W
 
 
-def _bs(t: Tensor) -> int:
+def _bs(t: Optional[Tensor]) -> int:
+    """Batch stride of a 4-D view in elements (0 for an absent operand)."""
+    if t is None:
+        return 0
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1] * t.shape[2] * t.shape[3])
 
 
@@ -45,8 +48,8 @@ def _vec16(t: Tensor) -> bool:
     return t.data_ptr() % 16 == 0 and _bs(t) % 4 == 0
 
 
-def _p(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+def _p(t: Optional[Tensor]) -> Optional[int]:
+    return t.data_ptr() if t is not None else None
 
 
 def new(N, Cc, H, W, like: Tensor) -> Tensor:
@@ -514,9 +517,8 @@ def attn_fused(qkv: Tensor, Cc: int, out: Optional[Tensor] = None, force_nw: int
         out = new(N, Cc, H, W, qkv)
     _chk4(out, "attn out")
     base = qkv.data_ptr()
-    check(lib().dcvic_attn_fused_f32(C.c_void_p(base), C.c_void_p(base + 4 * Cc * HW), C.c_void_p(base + 8 * Cc * HW),
-                                     C.c_longlong(3 * Cc * HW), _p(out), C.c_longlong(_bs(out)), N, Cc, HW,
-                                     C.c_float(float(int(Cc) ** (-0.5))), force_nw, _stream()), "attn_fused")
+    check(lib().dcvic_attn_fused_f32(base, base + 4 * Cc * HW, base + 8 * Cc * HW, 3 * Cc * HW, _p(out), _bs(out), N, Cc, HW,
+                                     float(int(Cc) ** (-0.5)), force_nw, _stream()), "attn_fused")
     return out
 
 
@@ -532,11 +534,10 @@ def groupnorm(x: Tensor, gamma: Tensor, beta: Tensor, groups: int = 32, eps: flo
         pt, n_pt = part
         if tuple(pt.shape) != (N, Cc, n_pt, 2) or not pt.is_contiguous():
             raise ValueError(f"groupnorm: partial statistics {tuple(pt.shape)} do not belong to a {tuple(x.shape)} map")
-        check(lib().dcvic_groupnorm_part_f32(_p(x), C.c_longlong(_bs(x)), _p(out), C.c_longlong(_bs(out)), _p(gamma), _p(beta),
-                                             N, Cc, H * W, groups, C.c_float(eps), act, _p(pt), n_pt, _stream()), "groupnorm_part")
+        check(lib().dcvic_groupnorm_part_f32(_p(x), _bs(x), _p(out), _bs(out), _p(gamma), _p(beta), N, Cc, H * W, groups, eps, act,
+                                             _p(pt), n_pt, _stream()), "groupnorm_part")
         return out
-    check(lib().dcvic_groupnorm_f32(_p(x), C.c_longlong(_bs(x)), _p(out), C.c_longlong(_bs(out)), _p(gamma), _p(beta),
-                                    N, Cc, H * W, groups, C.c_float(eps), act, _stream()), "groupnorm")
+    check(lib().dcvic_groupnorm_f32(_p(x), _bs(x), _p(out), _bs(out), _p(gamma), _p(beta), N, Cc, H * W, groups, eps, act, _stream()), "groupnorm")
     return out
 
 
@@ -545,7 +546,7 @@ def layernorm_c(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-5) -> Te
     if not x.is_contiguous():
         raise ValueError("layernorm_c needs a contiguous map")
     out = torch.empty_like(x)
-    check(lib().dcvic_layernorm_c_f32(_p(x), _p(out), _p(gamma), _p(beta), N, Cc, H * W, C.c_float(eps), _stream()), "layernorm_c")
+    check(lib().dcvic_layernorm_c_f32(_p(x), _p(out), _p(gamma), _p(beta), N, Cc, H * W, eps, _stream()), "layernorm_c")
     return out
 
 
@@ -575,10 +576,7 @@ def _ew(op: int, a: Tensor, b: Optional[Tensor], c: Optional[Tensor], w: float =
             _chk4(t, nm)
     if out is None:
         out = new(N, Cc, H, W, a)
-    check(lib().dcvic_ew_f32(op, _p(out), C.c_longlong(_bs(out)), _p(a), C.c_longlong(_bs(a)),
-                             _p(b), C.c_longlong(_bs(b) if b is not None else 0),
-                             _p(c), C.c_longlong(_bs(c) if c is not None else 0),
-                             N, Cc, H * W, C.c_float(w), act, _stream()), "ew")
+    check(lib().dcvic_ew_f32(op, _p(out), _bs(out), _p(a), _bs(a), _p(b), _bs(b), _p(c), _bs(c), N, Cc, H * W, w, act, _stream()), "ew")
     return out
 
 
@@ -607,9 +605,8 @@ def chan_affine(x: Tensor, scale: Tensor, shift: Tensor, add_: Optional[Tensor] 
         out = new(N, Cc, H, W, x)
     if scale.shape[-1] != Cc or scale.shape[0] not in (1, N):
         raise ValueError("chan_affine vectors must be [1|N, C]")
-    check(lib().dcvic_chan_affine_f32(_p(out), C.c_longlong(_bs(out)), _p(x), C.c_longlong(_bs(x)), _p(scale), _p(shift),
-                                      C.c_longlong(Cc if scale.shape[0] > 1 else 0), _p(add_),
-                                      C.c_longlong(_bs(add_) if add_ is not None else 0), N, Cc, H * W, _stream()), "chan_affine")
+    check(lib().dcvic_chan_affine_f32(_p(out), _bs(out), _p(x), _bs(x), _p(scale), _p(shift), Cc if scale.shape[0] > 1 else 0,
+                                      _p(add_), _bs(add_), N, Cc, H * W, _stream()), "chan_affine")
     return out
 
 
@@ -618,8 +615,8 @@ def copy_planes(dst: Tensor, src: Tensor, copyH: int, copyW: int, reflect: bool 
     Ns, Cs, sH, sW = _chk4(src, "copy src")
     if (N, Cc) != (Ns, Cs):
         raise ValueError("copy_planes N/C mismatch")
-    check(lib().dcvic_copy_planes_f32(_p(dst), C.c_longlong(_bs(dst)), dH, dW, _p(src), C.c_longlong(_bs(src)), sH, sW, N, Cc,
-                                      copyH, copyW, 1 if reflect else 0, _stream()), "copy_planes")
+    check(lib().dcvic_copy_planes_f32(_p(dst), _bs(dst), dH, dW, _p(src), _bs(src), sH, sW, N, Cc, copyH, copyW, 1 if reflect else 0,
+                                      _stream()), "copy_planes")
     return dst
 
 
@@ -641,8 +638,7 @@ def copy_window(dst: Tensor, src: Tensor) -> Tensor:
     if tuple(dst.shape) != tuple(src.shape) or dst.stride(3) != 1 or src.stride(3) != 1:
         raise ValueError("copy_window: views must have equal shapes and unit innermost stride")
     N, Cc, h, w = src.shape
-    check(lib().dcvic_copy_window_f32(_p(dst), C.c_longlong(dst.stride(0)), C.c_longlong(dst.stride(1)), C.c_longlong(dst.stride(2)),
-                                      _p(src), C.c_longlong(src.stride(0)), C.c_longlong(src.stride(1)), C.c_longlong(src.stride(2)),
+    check(lib().dcvic_copy_window_f32(_p(dst), dst.stride(0), dst.stride(1), dst.stride(2), _p(src), src.stride(0), src.stride(1), src.stride(2),
                                       N, Cc, h, w, _stream()), "copy_window")
     return dst
 
@@ -650,7 +646,7 @@ def copy_window(dst: Tensor, src: Tensor) -> Tensor:
 def absmax(x: Tensor) -> Tensor:
     N, Cc, H, W = _chk4(x, "absmax x")
     out = torch.empty(N, dtype=torch.float32, device=x.device)
-    check(lib().dcvic_absmax_f32(_p(x), C.c_longlong(_bs(x)), _p(out), N, C.c_longlong(Cc * H * W), _stream()), "absmax")
+    check(lib().dcvic_absmax_f32(_p(x), _bs(x), _p(out), N, Cc * H * W, _stream()), "absmax")
     return out
 
 
@@ -658,7 +654,7 @@ def crop_clamp(x: Tensor, H: int, W: int, want_u8: bool = False):
     N, Cc, Hs, Ws = _chk4(x, "crop_clamp x")
     y = new(N, Cc, H, W, x)
     y8 = torch.empty((N, H, W, Cc), dtype=torch.uint8, device=x.device) if want_u8 else None
-    check(lib().dcvic_crop_clamp_f32(_p(x), C.c_longlong(_bs(x)), Hs, Ws, _p(y), _p(y8), N, Cc, H, W, _stream()), "crop_clamp")
+    check(lib().dcvic_crop_clamp_f32(_p(x), _bs(x), Hs, Ws, _p(y), _p(y8), N, Cc, H, W, _stream()), "crop_clamp")
     return (y, y8) if want_u8 else y
 
 
@@ -708,19 +704,18 @@ def gaussian_rate(y: Optional[Tensor], sym_in: Optional[Tensor], mu: Tensor, sig
         si_bs = Cc * H * W
     ws = None
     if bits_out is not None:
-        ws = torch.empty(N * lib().dcvic_rate_blocks(C.c_longlong(Cc * H * W)), dtype=torch.float64, device=mu.device)
-    check(lib().dcvic_gaussian_rate_f32(_p(y), C.c_longlong(_bs(y) if y is not None else 0), _p(sym_in), _p(mu), _p(sigma),
-                                        C.c_longlong(_bs(mu)), _p(scale_table), scale_table.numel(), _p(y_hat),
-                                        C.c_longlong(_bs(y_hat) if y_hat is not None else 0), _p(sym_out), _p(index_out),
-                                        C.c_longlong(si_bs), _p(lik_out), _p(bits_out), _p(ws), N, Cc, H * W, _stream()), "gaussian_rate")
+        ws = torch.empty(N * lib().dcvic_rate_blocks(Cc * H * W), dtype=torch.float64, device=mu.device)
+    check(lib().dcvic_gaussian_rate_f32(_p(y), _bs(y), _p(sym_in), _p(mu), _p(sigma), _bs(mu), _p(scale_table), scale_table.numel(),
+                                        _p(y_hat), _bs(y_hat), _p(sym_out), _p(index_out), si_bs, _p(lik_out), _p(bits_out), _p(ws),
+                                        N, Cc, H * W, _stream()), "gaussian_rate")
 
 
 def neglog2_sum(lik: Tensor) -> Tensor:
     """Per-image bit cost -sum(log2 p) of a likelihood map [N, C, H, W] -> float32 [N]."""
     N, Cc, H, W = _chk4(lik, "neglog2 lik")
     out = torch.empty(N, dtype=torch.float32, device=lik.device)
-    ws = torch.empty(N * lib().dcvic_rate_blocks(C.c_longlong(Cc * H * W)), dtype=torch.float64, device=lik.device)
-    check(lib().dcvic_neglog2_sum_f32(_p(lik), C.c_longlong(_bs(lik)), _p(out), _p(ws), N, C.c_longlong(Cc * H * W), _stream()), "neglog2_sum")
+    ws = torch.empty(N * lib().dcvic_rate_blocks(Cc * H * W), dtype=torch.float64, device=lik.device)
+    check(lib().dcvic_neglog2_sum_f32(_p(lik), _bs(lik), _p(out), _p(ws), N, Cc * H * W, _stream()), "neglog2_sum")
     return out
 
 
@@ -739,8 +734,7 @@ def eb_rate(z: Optional[Tensor], packs, z_hat: Optional[Tensor], sym_out: Option
 def pmf_to_quantized_cdf(pmf: np.ndarray) -> np.ndarray:
     pmf = np.ascontiguousarray(pmf, dtype=np.float32)
     out = np.zeros(pmf.size + 1, dtype=np.int32)
-    check(lib().dcvic_pmf_to_quantized_cdf_host(pmf.ctypes.data_as(C.c_void_p), int(pmf.size), out.ctypes.data_as(C.c_void_p)),
-          "pmf_to_quantized_cdf")
+    check(lib().dcvic_pmf_to_quantized_cdf_host(pmf.ctypes.data, int(pmf.size), out.ctypes.data), "pmf_to_quantized_cdf")
     return out
 
 
@@ -749,11 +743,11 @@ class CdfTables:
         self.cdf = np.ascontiguousarray(cdf, dtype=np.int32)
         self.sizes = np.ascontiguousarray(sizes, dtype=np.int32)
         self.offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        h = lib().dcvic_tables_create_host(self.cdf.ctypes.data_as(C.c_void_p), int(self.cdf.shape[0]), int(self.cdf.shape[1]),
-                                           self.sizes.ctypes.data_as(C.c_void_p), self.offsets.ctypes.data_as(C.c_void_p))
+        h = lib().dcvic_tables_create_host(self.cdf.ctypes.data, int(self.cdf.shape[0]), int(self.cdf.shape[1]),
+                                           self.sizes.ctypes.data, self.offsets.ctypes.data)
         if not h:
             check(-1, "tables_create")
-        self.h = C.c_void_p(h)
+        self.h = h
 
     def __del__(self):
         try:
@@ -769,9 +763,8 @@ class CdfTables:
         cap = int(n) * 8 + 64
         out = np.empty((ns, cap), dtype=np.uint8)
         lens = np.zeros(ns, dtype=np.int64)
-        check(lib().dcvic_rans_encode_batch_host(self.h, symbols.ctypes.data_as(C.c_void_p), indexes.ctypes.data_as(C.c_void_p),
-                                                 ns, C.c_longlong(n), out.ctypes.data_as(C.c_void_p), C.c_longlong(cap),
-                                                 lens.ctypes.data_as(C.c_void_p), threads), "rans_encode")
+        check(lib().dcvic_rans_encode_batch_host(self.h, symbols.ctypes.data, indexes.ctypes.data, ns, n, out.ctypes.data, cap,
+                                                 lens.ctypes.data, threads), "rans_encode")
         return [out[i, : lens[i]].tobytes() for i in range(ns)]
 
     def decoders(self, streams: Sequence[bytes]) -> "DecoderSet":
@@ -785,7 +778,7 @@ class DecoderSet:
         self._bufs = []
         for s in streams:
             buf = np.frombuffer(s, dtype=np.uint8)
-            h = lib().dcvic_rans_decoder_create_host(buf.ctypes.data_as(C.c_void_p), C.c_longlong(buf.size))
+            h = lib().dcvic_rans_decoder_create_host(buf.ctypes.data, buf.size)
             if not h:
                 self.close()
                 check(-4, "rans_decoder_create")
@@ -797,13 +790,12 @@ class DecoderSet:
         ns, n = indexes.shape
         assert ns == len(self.handles)
         out = np.empty((ns, n), dtype=np.int32)
-        check(lib().dcvic_rans_decode_batch_host(self.t.h, self.arr, indexes.ctypes.data_as(C.c_void_p), ns, C.c_longlong(n),
-                                                 out.ctypes.data_as(C.c_void_p), threads), "rans_decode")
+        check(lib().dcvic_rans_decode_batch_host(self.t.h, self.arr, indexes.ctypes.data, ns, n, out.ctypes.data, threads), "rans_decode")
         return out
 
     def close(self):
         for h in self.handles:
-            lib().dcvic_rans_decoder_destroy_host(C.c_void_p(h))
+            lib().dcvic_rans_decoder_destroy_host(h)
         self.handles = []
 
     def __del__(self):

@@ -9,7 +9,6 @@ ones.  The 11x11 / stride-4 / pad-2 stem runs as a 3x3 / stride-1 convolution ov
 space-to-depth(4) image (kernel zero-padded to 12x12) -- same sums, conv kernels limited to 25 taps."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import List
 
 import torch
@@ -85,14 +84,14 @@ def s2d(ctx: Ctx, x: Var, r: int, pad: int, k: int) -> Var:
     N, Cc, H, W = _chk4(xd, "s2d x")
     Ho, Wo = (H + 2 * pad - k) // r + 1 + (k - 1) // r, (W + 2 * pad - k) // r + 1 + (k - 1) // r
     y = torch.empty((N, Cc * r * r, Ho, Wo), dtype=torch.float32, device=xd.device)
-    check(lib().dcvic_s2d_f32(_p(xd), _p(y), C.c_longlong(N * Cc), H, W, r, pad, Ho, Wo, 0, _stream()), "s2d")
+    check(lib().dcvic_s2d_f32(_p(xd), _p(y), N * Cc, H, W, r, pad, Ho, Wo, 0, _stream()), "s2d")
     out = Var(y)
 
     def back():
         if out.grad is None or not x.needs_grad:
             return
         dx = torch.empty_like(xd)
-        check(lib().dcvic_s2d_f32(_p(A._dense(out.grad)), _p(dx), C.c_longlong(N * Cc), H, W, r, pad, Ho, Wo, 1, _stream()), "s2d_bwd")
+        check(lib().dcvic_s2d_f32(_p(A._dense(out.grad)), _p(dx), N * Cc, H, W, r, pad, Ho, Wo, 1, _stream()), "s2d_bwd")
         A.acc(x, dx)
     ctx.tape.append(back)
     return out
@@ -104,14 +103,14 @@ def maxpool3s2(ctx: Ctx, x: Var) -> Var:
     Ho, Wo = (H - 3) // 2 + 1, (W - 3) // 2 + 1
     y = torch.empty((N, Cc, Ho, Wo), dtype=torch.float32, device=xd.device)
     am = torch.empty((N, Cc, Ho, Wo), dtype=torch.uint8, device=xd.device)
-    check(lib().dcvic_maxpool3s2_f32(_p(xd), _p(y), _p(am), None, None, C.c_longlong(N * Cc), H, W, _stream()), "maxpool")
+    check(lib().dcvic_maxpool3s2_f32(_p(xd), _p(y), _p(am), None, None, N * Cc, H, W, _stream()), "maxpool")
     out = Var(y)
 
     def back():
         if out.grad is None or not x.needs_grad:
             return
         dx = torch.empty_like(xd)
-        check(lib().dcvic_maxpool3s2_f32(None, None, _p(am), _p(A._dense(out.grad)), _p(dx), C.c_longlong(N * Cc), H, W, _stream()), "maxpool_bwd")
+        check(lib().dcvic_maxpool3s2_f32(None, None, _p(am), _p(A._dense(out.grad)), _p(dx), N * Cc, H, W, _stream()), "maxpool_bwd")
         A.acc(x, dx)
     ctx.tape.append(back)
     return out
@@ -144,7 +143,7 @@ def lpips_loss(ctx: Ctx, L: LPIPSAlex, real: Tensor, fake: Var, weight: float) -
         _, Cc, H, W = f1d.shape
         pix = torch.empty((N, H * W), dtype=torch.float32, device=f1d.device)
         df1 = torch.empty_like(f1d)
-        check(lib().dcvic_lpips_tap_f32(_p(f0), _p(f1d), _p(w), _p(pix), _p(df1), N, Cc, H * W, C.c_float(weight / N), _stream()), "lpips_tap")
+        check(lib().dcvic_lpips_tap_f32(_p(f0), _p(f1d), _p(w), _p(pix), _p(df1), N, Cc, H * W, weight / N, _stream()), "lpips_tap")
         A.acc(f1, df1)
         v = K.reduce_loss(3, pix, None, weight / (N * H * W))
         total = v if total is None else K.ew(10, None, total, v)

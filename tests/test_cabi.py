@@ -22,6 +22,86 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SYMBOLS) == names
 
 
+def declared_prototypes():
+    """{name: (restype, [argtypes])} of every function include/dcvic.h declares, in ctypes terms: the mapping the binding uses
+    (every pointer parameter a c_void_p, a const char* return a c_char_p, any other pointer return an opaque c_void_p)."""
+    import ctypes as C
+    scalars = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+    txt = open(os.path.join(ROOT, "include", "dcvic.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"^(\w[\w \t]*?\**)\s*\b(dcvic_\w+)\s*\(([^()]*)\)\s*;", txt, flags=re.M):
+        ret = " ".join(ret.split())
+        if ret == "const char*":
+            restype = C.c_char_p
+        elif "*" in ret:
+            restype = C.c_void_p
+        else:
+            restype = None if ret == "void" else scalars[ret]
+        argtypes = []
+        for prm in ([] if params.strip() == "void" else params.split(",")):
+            if "*" in prm:
+                argtypes.append(C.c_void_p)
+                continue
+            words = prm.split()                      # a scalar type, then an optional parameter name
+            ty = " ".join(words)
+            argtypes.append(scalars[ty] if ty in scalars else scalars[" ".join(words[:-1])])
+        assert name not in protos, f"{name} declared twice"
+        protos[name] = (restype, argtypes)
+    return protos
+
+
+def signature_mismatches(table, protos):
+    """Every disagreement between a "return:parameters" table (_lib.SIGNATURES) and the header's prototypes, as messages."""
+    bad = [f"{n}: declared in include/dcvic.h but absent from the table" for n in protos if n not in table]
+    bad += [f"{n}: in the table but not declared in include/dcvic.h" for n in table if n not in protos]
+    for n in table:
+        if n in protos:
+            ret, params = table[n].split(":")
+            have = (_lib._CTYPE[ret], [_lib._CTYPE[c] for c in params])
+            if have != protos[n]:
+                bad.append(f"{n}: the table says {have}, the header {protos[n]}")
+    return bad
+
+
+def test_signature_table_matches_header_prototypes():
+    """_lib.SIGNATURES states every prototype of include/dcvic.h type for type, and the loaded library's functions carry exactly those
+    restype / argtypes.  The comparison itself is shown to catch a long long declared as int, a missing parameter and a function
+    missing from the table."""
+    import ctypes as C
+    protos = declared_prototypes()
+    assert len(protos) == 89 and sorted(protos) == declared_symbols()
+    # the parser, on prototypes read by eye: optional parameter names, every scalar type, each kind of return
+    assert protos["dcvic_tables_destroy_host"] == (None, [C.c_void_p])
+    assert protos["dcvic_last_error"] == (C.c_char_p, [])
+    assert protos["dcvic_conv_packed_bytes"] == (C.c_size_t, [C.c_void_p])
+    assert protos["dcvic_rans_decoder_create_host"] == (C.c_void_p, [C.c_void_p, C.c_longlong])
+    assert protos["dcvic_pair_moments_workspace_doubles"] == (C.c_longlong, [C.c_longlong, C.c_longlong])
+    assert protos["dcvic_reduce_loss_f32"] == (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_double,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p])
+    assert protos["dcvic_clip_scale_f32"] == (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p])
+
+    assert signature_mismatches(_lib.SIGNATURES, protos) == []
+    L = _lib.lib()
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+    def broken(name, sig):
+        t = dict(_lib.SIGNATURES)
+        if sig is None:
+            del t[name]
+        else:
+            t[name] = sig
+        return signature_mismatches(t, protos)
+    assert _lib.SIGNATURES["dcvic_neglog2_sum_f32"] == "i:pqppiqp"
+    for sig in ("i:pippiqp", "i:pqppiip",      # a long long declared as int
+                "i:pqppiq", "i:qppiqp",         # a parameter missing
+                "i:pqppiqpp", "q:pqppiqp", None):
+        bad = broken("dcvic_neglog2_sum_f32", sig)
+        assert len(bad) == 1 and bad[0].startswith("dcvic_neglog2_sum_f32:"), (sig, bad)
+
+
 def test_error_reporting_without_gpu():
     L = _lib.lib()
     assert L.dcvic_version() >= 100
@@ -42,15 +122,12 @@ def test_error_reporting_without_gpu():
 def test_wino_packed_bytes_host_formula():
     """dcvic_wino_packed_bytes is a host-side size query (no GPU): one 32 KiB slab (16 positions x 8 channels x 64 output
     channels, fp32) per (64-channel tile, 8-channel chunk), both rounded up."""
-    import ctypes as C
     from dc_vic_amd import _lib
     L = _lib.lib()
-    L.dcvic_wino_packed_bytes.restype = C.c_size_t
     for cin, cout in ((128, 128), (704, 512), (8, 64), (20, 96), (256, 3)):
         assert L.dcvic_wino_packed_bytes(cin, cout) == ((cout + 63) // 64) * ((cin + 7) // 8) * 16 * 8 * 64 * 4
     assert L.dcvic_wino_packed_bytes(0, 64) == 0
     # F(4x4, 3x3): one 72 KiB slab (2 k-steps x 36 positions x 4 channels x 64 output channels) per (64-channel tile, 8-channel chunk)
-    L.dcvic_wino44_packed_bytes.restype = C.c_size_t
     for cin, cout in ((256, 256), (704, 512), (8, 64), (128, 200)):
         assert L.dcvic_wino44_packed_bytes(cin, cout) == ((cout + 63) // 64) * ((cin + 7) // 8) * 2 * 36 * 4 * 64 * 4
     assert L.dcvic_wino44_packed_bytes(64, 0) == 0

@@ -1,4 +1,4 @@
-"""ctypes binding of libdcvic_hip.so (include/dcvic.h).  The library is REQUIRED: there is no
+"""ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h).  The library is REQUIRED: there is no
 fallback path -- if it is missing or an entry point fails, the caller gets an exception."""
 from __future__ import annotations
 
@@ -99,6 +99,10 @@ SIGNATURES = {
     "dcvic_msssim_workspace_bytes": "q:iiii", "dcvic_msssim_psnr_f64": "i:ppiiiippppqp",
 }
 SYMBOLS = list(SIGNATURES)
+# include/dcvic_loss.h: the loss entry points declared outside dcvic.h's frozen table, in the same notation (csrc/focal.hip)
+LOSS_SIGNATURES = {
+    "dcvic_focal_ce_workspace_doubles": "q:ii", "dcvic_focal_ce_f32": "i:ppddpppiiip",
+}
 
 _lib = None
 
@@ -117,7 +121,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python dc_vic_amd/csrc/build.py` "
             "(or __graft_entry__.build()). dc_vic_amd has no fallback path.")
     L = C.CDLL(LIB_PATH)
-    for name, sig in SIGNATURES.items():     # the package's only restype / argtypes assignments; other symbols stay untyped
+    for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
         fn = getattr(L, name)                # AttributeError names a symbol the library lacks
         ret, params = sig.split(":")
         fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[c] for c in params]

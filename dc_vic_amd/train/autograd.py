@@ -470,6 +470,19 @@ def cross_entropy_loss(ctx: Ctx, logits: Var, target: Tensor, weight: float) -> 
     return val
 
 
+def focal_cross_entropy_loss(ctx: Ctx, logits: Var, target: Tensor, weight: float, gamma: float, reduction: str = "mean") -> Tensor:
+    """weight * reduce((1 - p_t)^gamma * CrossEntropy(logits [N, C, H, W], target [N, H, W])) with reduce = mean over N*H*W or sum
+    (cross_entropy_loss.py:33-53): value and gradient from one pass of csrc/focal.hip; the gradient is seeded into `logits`."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"focal_cross_entropy_loss: reduction {reduction!r}, expected 'mean' or 'sum'")
+    ld = _dense(logits.data)
+    N, Cc, H, W = ld.shape
+    val, dl = K.focal_ce(ld, target.contiguous(), gamma, weight / (N * H * W) if reduction == "mean" else weight, want_grad=logits.needs_grad)
+    if dl is not None:
+        acc(logits, dl)
+    return val
+
+
 def oasis_gan_loss(ctx: Ctx, logits: Var, target: Tensor, is_real: bool, weight: float, want_score: bool = False):
     """weight * CrossEntropy(logits [N, C, H, W], target + 1 if is_real else 0), mean over N*H*W (src/losses/oasis_gan_loss.py:40-79):
     value, gradient and -- with want_score -- mean(logits[:, 1:]) from one pass of csrc/oasis.hip.  Returns the value, or

@@ -145,6 +145,21 @@ def oasis_ce(logits: Tensor, target: Optional[Tensor], is_real: bool, scale: flo
     return loss, dl, score
 
 
+def focal_ce(logits: Tensor, target: Tensor, gamma: float, scale: float, want_grad: bool = True):
+    """Focal cross entropy (csrc/focal.hip) in one pass over logits [N, C, H, W]: (loss, dlogits or None) with
+    loss = scale * sum_positions (1 - p_t)^gamma * CE(logits, target) and dlogits its gradient; gamma is 0 or >= 1."""
+    if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("focal_ce: contiguous fp32 logits [N, C, H, W]")
+    N, Cc, H, W = logits.shape
+    if target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != N * H * W:
+        raise ValueError(f"focal_ce: contiguous int64 targets with {N * H * W} elements")
+    ws = _workspace(int(lib().dcvic_focal_ce_workspace_doubles(N, H * W)), logits.device, "focal_ws", torch.float64)
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    check(lib().dcvic_focal_ce_f32(_p(logits), _p(target), float(gamma), scale, _p(loss), _p(dl), _p(ws), N, Cc, H * W, _stream()), "focal_ce")
+    return loss, dl
+
+
 def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, b1: float, b2: float, eps: float, step: int, gscale: Optional[Tensor]) -> None:
     check(lib().dcvic_adam_step_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, step, _p(gscale), _stream()), "adam_step")
 

@@ -1,0 +1,203 @@
+"""The code losses of the reference's `loss` section (src/losses/cross_entropy_loss.py) on the training tape, and the host-side
+reading of that section (config/exp1_stage1_3.yaml:61-79): every entry's `type` and keywords are either honoured or refused
+with the YAML key and the value -- none is read and dropped.  `read_loss_section` is pure: no GPU, no model."""
+from __future__ import annotations
+
+from typing import Any, Dict, Optional
+
+from ..registry import LOSS_REGISTRY
+from . import autograd as A
+
+Tensor = Any
+
+
+def check_focal_gamma(gamma) -> float:
+    """gamma is 0 (plain cross entropy) or >= 1: for 0 < gamma < 1 the derivative of (1 - p_t)^gamma is unbounded at p_t = 1
+    (torch's autograd returns NaN there), a negative gamma is unbounded in value."""
+    try:
+        g = float(gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"gamma: {gamma!r} is not a number")
+    if not (g == 0.0 or g >= 1.0) or g == float("inf"):
+        raise ValueError(f"gamma: {gamma} is not supported, it must be 0 or >= 1 (the gradient is unbounded at p_t = 1 for 0 < gamma < 1)")
+    return g
+
+
+@LOSS_REGISTRY.register()
+class CrossEntropyLoss:
+    """cross_entropy_loss.py:11-29: loss_weight * nn.CrossEntropyLoss()(logits [N, C, H, W], target [N, H, W]).  The value and the
+    gradient come from dcvic_cross_entropy_f32 + reduce_loss, as the trainer's code loss always did."""
+
+    def __init__(self, loss_weight: float, ce_kwargs: Optional[dict] = None, **extra):
+        if extra:
+            raise ValueError(f"CrossEntropyLoss: unknown keyword(s) {sorted(extra)}")
+        if ce_kwargs:
+            raise ValueError(f"ce_kwargs: {dict(ce_kwargs)} is not supported (class weights, ignore_index and label smoothing are not built): leave it empty")
+        self.loss_weight = float(loss_weight)
+
+    def __call__(self, ctx: A.Ctx, logits: A.Var, target: Tensor) -> Tensor:
+        return A.cross_entropy_loss(ctx, logits, target, self.loss_weight)
+
+
+@LOSS_REGISTRY.register()
+class FocalCrossEntropyLoss:
+    """cross_entropy_loss.py:32-53: loss_weight * reduce((1 - p_t)^gamma * CE) with reduction mean or sum, one pass of csrc/focal.hip.
+    `reduction: none` returns a per-position map for the per-sample beta weighting of the rate-distortion trainers, which are not
+    built; the reference forwards further keywords to nn.CrossEntropyLoss, none of which is built either."""
+
+    def __init__(self, loss_weight: float, gamma: float, reduction: str = "mean", **kwargs):
+        if kwargs:
+            raise ValueError(f"FocalCrossEntropyLoss: unknown keyword(s) {sorted(kwargs)} (nn.CrossEntropyLoss options are not built)")
+        if reduction not in ("mean", "sum"):
+            why = "needs the per-sample weighting of the rate-distortion trainers, which are not built" if reduction == "none" else "is unknown"
+            raise ValueError(f"reduction: {reduction} {why}; use mean or sum")
+        self.loss_weight, self.gamma, self.reduction = float(loss_weight), check_focal_gamma(gamma), reduction
+
+    def __call__(self, ctx: A.Ctx, logits: A.Var, target: Tensor) -> Tensor:
+        return A.focal_cross_entropy_loss(ctx, logits, target, self.loss_weight, self.gamma, self.reduction)
+
+
+# ---------------------------------------------------------------------------------------------------- the YAML's `loss` section
+# the reference's trainers with a rate term and per-sample beta weights (config/exp1_stage1_1.yaml, exp1_stage1_2.yaml): not built,
+# scripts/train.py refuses them by `trainer.type`.  Their `rate_loss` entry and `reduction: none` are those trainers' business and
+# are passed over here; in a GAN-stage config both are refused.
+RATE_DISTORTION_TRAINERS = ("RateDistortionVqCodeTrainer", "DualBetaCondRateDistortionVqCodeTrainer")
+_ENTRIES = ("distortion_loss", "perceptual_loss", "gan_loss", "code_distortion_loss", "code_ce_loss", "rate_loss")
+_WEIGHT_NAME = {"distortion_loss": "distortion", "perceptual_loss": "perceptual", "gan_loss": "gan", "code_distortion_loss": "code_distortion",
+                "code_ce_loss": "code_ce"}
+
+
+def mse_distortion_factor(normalize_img: bool, mse_scale: str) -> float:
+    """The factor of MSELoss (distortion_loss.py:11-39) on mean((a - b)^2) of the [-1, 1] images: normalised images are mapped to
+    [0, 1] or [0, 255] first (alpha 1), un-normalised ones are scaled by alpha = 1/4 or 255^2 / 4000."""
+    if mse_scale == "0_1":
+        return 0.25
+    return (255.0 / 2.0) ** 2 if normalize_img else 255.0 ** 2 / 4000.0
+
+
+def _refuse(key: str, value, why: str):
+    raise SystemExit(f"loss.{key}: {value} {why}")
+
+
+def _only(entry: dict, name: str, allowed) -> None:
+    for k in entry:
+        if k not in allowed:
+            _refuse(f"{name}.{k}", entry[k], f"is not a keyword of {entry.get('type')} that is built (known: {', '.join(allowed)})")
+
+
+def read_loss_section(opt) -> Dict[str, Any]:
+    """What the GAN-stage trainers need from `opt['loss']`, or SystemExit naming the YAML key and the value.  An absent entry or an
+    absent `type` keeps the trainer's defaults (CrossEntropyLoss, MSELoss on [0, 1], VanillaMSELoss mean, LPIPS alex).  Returns
+      weights              {trainer weight name: loss_weight} of the entries that give one
+      code_ce              dict(type, gamma, reduction) -- `type` None for the default
+      distortion_factor    factor on mean((a - b)^2) of the [-1, 1] images (times loss_weight)
+      code_distortion_reduction  'mean' or 'sum'
+      per_sample           True when `trainer.type` names a rate-distortion trainer (its `reduction: none` entries are kept as read)
+      line                 the `[train] losses:` log text
+    `gan_loss` is judged by scripts/train.py's choose_gan_trainer; only its weight is read here."""
+    try:
+        loss = opt["loss"]
+    except (KeyError, TypeError):
+        loss = None
+    loss = dict(loss) if loss else {}
+    try:
+        t_type = opt["trainer"]["type"]
+    except (KeyError, TypeError):
+        t_type = None
+    per_sample = t_type in RATE_DISTORTION_TRAINERS
+    for k in loss:
+        if k not in _ENTRIES:
+            _refuse(k, loss[k], f"is not a loss entry of the GAN-stage trainers (known: {', '.join(_ENTRIES)})")
+    entries = {k: dict(loss.get(k) or {}) for k in _ENTRIES if k in loss}
+    weights = {}
+    for k, name in _WEIGHT_NAME.items():
+        v = entries.get(k, {}).get("loss_weight")
+        if v is not None:
+            try:
+                weights[name] = float(v)
+            except (TypeError, ValueError):
+                _refuse(f"{k}.loss_weight", v, "is not a number")
+
+    def reduction_of(name: str, e: dict, allowed=("mean", "sum")) -> str:
+        r = e.get("reduction", "mean")
+        if r == "none" and per_sample:
+            return r
+        if r == "none":
+            _refuse(f"{name}.reduction", r, "needs the per-sample weighting of the rate-distortion trainers, which are not built; use mean or sum")
+        if r not in allowed:
+            _refuse(f"{name}.reduction", r, f"is unknown, expected {' or '.join(allowed)}")
+        return r
+
+    # rate_loss: no GAN-stage trainer has a rate term (fix_entropy_models)
+    if "rate_loss" in entries and not per_sample:
+        _refuse("rate_loss", entries["rate_loss"].get("type", entries["rate_loss"]), "has no place in the GAN-stage trainers: they train no rate term")
+
+    # code_ce_loss
+    e = entries.get("code_ce_loss", {})
+    code_ce = dict(type=e.get("type"), gamma=0.0, reduction="mean")
+    if e.get("type") == "CrossEntropyLoss":
+        _only(e, "code_ce_loss", ("type", "loss_weight", "ce_kwargs"))
+        if e.get("ce_kwargs"):
+            _refuse("code_ce_loss.ce_kwargs", dict(e["ce_kwargs"]), "is not supported (nn.CrossEntropyLoss options are not built): leave it empty")
+    elif e.get("type") == "FocalCrossEntropyLoss":
+        _only(e, "code_ce_loss", ("type", "loss_weight", "gamma", "reduction"))
+        if "gamma" not in e:
+            _refuse("code_ce_loss.gamma", None, "is missing: FocalCrossEntropyLoss has no default gamma")
+        try:
+            code_ce["gamma"] = check_focal_gamma(e["gamma"])
+        except ValueError as err:
+            raise SystemExit(f"loss.code_ce_loss.{err}")
+        code_ce["reduction"] = reduction_of("code_ce_loss", e)
+    elif e.get("type") is not None:
+        _refuse("code_ce_loss.type", e["type"], "is not built, expected CrossEntropyLoss or FocalCrossEntropyLoss")
+
+    # distortion_loss
+    e = entries.get("distortion_loss", {})
+    factor, d_desc = 0.25, "MSELoss on [0, 1]"
+    if e.get("type") == "MSELoss":
+        _only(e, "distortion_loss", ("type", "loss_weight", "normalize_img", "mse_scale"))
+        norm, scale = e.get("normalize_img", False), e.get("mse_scale", "0_255")
+        if not isinstance(norm, bool):
+            _refuse("distortion_loss.normalize_img", norm, "is not a boolean")
+        if scale not in ("0_255", "0_1"):
+            _refuse("distortion_loss.mse_scale", repr(scale), "is unknown, expected '0_255' or '0_1'")
+        factor = mse_distortion_factor(norm, scale)
+        d_desc = f"MSELoss(normalize_img={norm}, mse_scale={scale})"
+    elif e.get("type") is not None:
+        _refuse("distortion_loss.type", e["type"], "is not built, expected MSELoss")
+
+    # code_distortion_loss
+    e = entries.get("code_distortion_loss", {})
+    cd_red = "mean"
+    if e.get("type") == "VanillaMSELoss":
+        _only(e, "code_distortion_loss", ("type", "loss_weight", "reduction"))
+        cd_red = reduction_of("code_distortion_loss", e)
+    elif e.get("type") is not None:
+        _refuse("code_distortion_loss.type", e["type"], "is not built, expected VanillaMSELoss")
+
+    # perceptual_loss
+    e = entries.get("perceptual_loss", {})
+    if e.get("type") == "LPIPSLoss":
+        _only(e, "perceptual_loss", ("type", "loss_weight", "net", "range_norm"))
+        net = e.get("net", "vgg")                      # perceptual_loss.py:12, the reference's default
+        if net != "alex":
+            _refuse("perceptual_loss.net", net if "net" in e else "vgg (LPIPSLoss's default)", "is not built, expected alex")
+        if e.get("range_norm", False):
+            _refuse("perceptual_loss.range_norm", e["range_norm"], "is not built: the trainer's images are in [-1, 1] already, set it to false")
+    elif e.get("type") is not None:
+        _refuse("perceptual_loss.type", e["type"], "is not built, expected LPIPSLoss")
+
+    ce_desc = "CrossEntropyLoss" if code_ce["type"] != "FocalCrossEntropyLoss" else f"FocalCrossEntropyLoss(gamma={code_ce['gamma']:g}, {code_ce['reduction']})"
+    line = (f"distortion {d_desc} factor {factor:g}; perceptual LPIPSLoss(net=alex); code_distortion VanillaMSELoss({cd_red}); "
+            f"code_ce {ce_desc}")
+    return dict(weights=weights, code_ce=code_ce, distortion_factor=factor, code_distortion_reduction=cd_red, per_sample=per_sample, line=line)
+
+
+def build_code_ce_loss(code_ce: Dict[str, Any], loss_weight: float):
+    """The loss object for read_loss_section's `code_ce`, or None for the trainer's default."""
+    if code_ce.get("type") is None:
+        return None
+    cls = LOSS_REGISTRY.get(code_ce["type"])
+    if code_ce["type"] == "FocalCrossEntropyLoss":
+        return cls(loss_weight, code_ce["gamma"], code_ce["reduction"])
+    return cls(loss_weight)

@@ -4,7 +4,9 @@ Mirrors src/trainer/dual_cond_gan_distortion_vq_code_trainer.py:24-300 (`DualBet
 `optimize_parameters` = G step (run_comp_model with is_train=True / fix_entropy_models=True / sample_batch_beta, calc_g_loss,
 backward, clip_grad_norm_, Adam, MultiStepLR) followed by the D step (run_discriminator, calc_d_loss, backward, Adam).
 Loss definitions: config/exp1_stage1_3.yaml:61-79 (MSELoss x50 on [0,1] images, VanillaGANLoss x0.01, VanillaMSELoss x1 on
-the predicted code embedding, CrossEntropyLoss x0.5 on the code logits).
+the predicted code embedding, CrossEntropyLoss x0.5 on the code logits).  Stage 1-3 (config/exp1_stage1_3.yaml) is the same trainer
+without `use_selected_beta_pairs`: beta_rate and beta_vq come per sample from `sample_beta_grid`; the code loss may be the
+FocalCrossEntropyLoss of train/losses.py.
 
 Differences, stated:
   * LPIPS (perceptual_loss): the `lpips` wheel and its AlexNet / head weights cannot be fetched offline.  The term is computed
@@ -58,6 +60,14 @@ def allreduce_mean_(flat: Tensor, dist, bucket_bytes: int = 64 << 20) -> int:
     return len(works)
 
 
+def sample_beta_grid(rng: np.random.RandomState, max_beta: float, num_levels: int, n: int) -> Tensor:
+    """hyperprior_dc_vic_model.py:91-97 (`_sample_beta`): n draws from the grid max_beta * k / num_levels, k = 0..num_levels (both
+    ends reachable), as a float32 tensor [n].  The reference draws from numpy's global state; here the generator is passed in."""
+    i = rng.randint(0, num_levels + 1, n)
+    beta = np.float32(max_beta) * (i.astype(np.float32) / np.float32(num_levels))
+    return torch.from_numpy(np.asarray(beta, dtype=np.float32))
+
+
 def loss_anomaly(total: float, dist, device=None) -> bool:
     """base_trainer.py:235-245 skips a step whose total loss is non-finite or > 1e4.  With several ranks the decision must be
     COLLECTIVE: a rank that returned early while the others entered the gradient all-reduce would leave them blocked in RCCL
@@ -99,7 +109,11 @@ class Adam:
 class DualBetaCondGanDistortionVqCodeTrainer:
     def __init__(self, model, discriminator, lr_g: float = 1e-4, lr_d: float = 1e-4, milestones=(300000,), gamma: float = 0.1,
                  clip_max_norm: Optional[float] = 1.0, loss_weights: Optional[Dict[str, float]] = None, sample_beta_batch: bool = True,
-                 dist=None, seed: int = 0, d_milestones=None, d_gamma: Optional[float] = None, lpips_state: Optional[Dict[str, Tensor]] = None):
+                 dist=None, seed: int = 0, d_milestones=None, d_gamma: Optional[float] = None, lpips_state: Optional[Dict[str, Tensor]] = None,
+                 code_ce_loss=None, distortion_factor: float = 0.25, code_distortion_reduction: str = "mean"):
+        """`code_ce_loss`: a loss object of train/losses.py (CrossEntropyLoss / FocalCrossEntropyLoss, carrying its own weight) or None
+        for CrossEntropyLoss x loss_weights['code_ce']; `distortion_factor`: MSELoss's factor on mean((a - b)^2) of the [-1, 1] images
+        (0.25 = the [0, 1] scale of the shipped configs); `code_distortion_reduction`: VanillaMSELoss's mean or sum."""
         self.model, self.D = model, discriminator
         dev = next(model.decoder.parameters()).device
         self.device = dev
@@ -114,7 +128,12 @@ class DualBetaCondGanDistortionVqCodeTrainer:
         self.w = dict(DEFAULT_LOSS)
         if loss_weights:
             self.w.update(loss_weights)
+        if code_distortion_reduction not in ("mean", "sum"):
+            raise ValueError(f"code_distortion_reduction {code_distortion_reduction!r}: expected 'mean' or 'sum'")
+        self.code_ce_loss, self.distortion_factor, self.code_distortion_reduction = code_ce_loss, float(distortion_factor), code_distortion_reduction
         self.sample_beta_batch = sample_beta_batch
+        self.last_beta_rate: Optional[Tensor] = None   # the pair the last optimize_parameters trained with
+        self.last_beta_vq: Optional[Tensor] = None
         self.dist = dist
         self.rng = np.random.RandomState(seed)
         self.last_fake: Optional[Tensor] = None
@@ -200,6 +219,15 @@ class DualBetaCondGanDistortionVqCodeTrainer:
         i = self.rng.randint(0, len(m.selected_beta_rate), n)
         return (torch.Tensor([m.selected_beta_rate[k] for k in i]).float(), torch.Tensor([m.selected_beta_vq[k] for k in i]).float())
 
+    # hyperprior_dc_vic_model.py:143-161 (data_preprocess without selected pairs): beta_rate first, then beta_vq
+    def sample_beta_pair(self, n: int) -> Tuple[Tensor, Tensor]:
+        m = self.model
+        if getattr(m, "use_selected_beta_pairs", False):
+            return self.sample_selected_beta_pair(n)
+        beta_rate = sample_beta_grid(self.rng, m.max_beta_rate, m.num_beta_levels, n)
+        beta_vq = sample_beta_grid(self.rng, m.max_beta_vq, m.num_beta_levels, n)
+        return beta_rate, beta_vq
+
     @torch.no_grad()
     def generator_forward(self, ctx: Ctx, real: Tensor, vq_indices: Optional[Tensor], beta_rate, beta_vq):
         """run_comp_model (:116-133) -> forward (hyperprior_dc_vic_model.py:208-274, is_train, fix_entropy_models)."""
@@ -223,7 +251,7 @@ class DualBetaCondGanDistortionVqCodeTrainer:
         """:192-234; each term seeds its gradient on the tape."""
         w = self.w
         log = {}
-        log["distortion"] = A.mse_loss(ctx, o["fake"], o["real"], w["distortion"] * 0.25)        # MSELoss on [0,1]: ((a+1)/2-(b+1)/2)^2
+        log["distortion"] = A.mse_loss(ctx, o["fake"], o["real"], w["distortion"] * self.distortion_factor)   # 0.25: MSELoss on [0,1], ((a+1)/2-(b+1)/2)^2
         if self.lpips is not None:
             from .lpips import lpips_loss
             log["perceptual"] = lpips_loss(ctx, self.lpips, o["real"], o["fake"], w["perceptual"])
@@ -231,8 +259,12 @@ class DualBetaCondGanDistortionVqCodeTrainer:
             log["perceptual"] = torch.zeros(1, device=self.device)
         g_fake = nets.discriminator_forward(ctx, self.D, o["fake"], beta_rate, beta_vq)
         log["adv"] = self.calc_adv_loss(ctx, g_fake, o["gt_vq_indices"])
-        log["code_distortion"] = A.mse_loss(ctx, o["pred_embed"], o["gt_vq_latent"], w["code_distortion"])
-        log["code_ce"] = A.cross_entropy_loss(ctx, o["logits"], o["gt_vq_indices"], w["code_ce"])
+        w_cd = w["code_distortion"] * (o["gt_vq_latent"].numel() if self.code_distortion_reduction == "sum" else 1)
+        log["code_distortion"] = A.mse_loss(ctx, o["pred_embed"], o["gt_vq_latent"], w_cd)
+        if self.code_ce_loss is None:
+            log["code_ce"] = A.cross_entropy_loss(ctx, o["logits"], o["gt_vq_indices"], w["code_ce"])
+        else:
+            log["code_ce"] = self.code_ce_loss(ctx, o["logits"], o["gt_vq_indices"])
         return log
 
     def calc_adv_loss(self, ctx: Ctx, g_fake, gt_vq_indices: Tensor) -> Tensor:
@@ -245,7 +277,8 @@ class DualBetaCondGanDistortionVqCodeTrainer:
         n = real.shape[0]
         beta_rate, beta_vq = data_dict.get("beta_rate"), data_dict.get("beta_vq")
         if beta_rate is None or beta_vq is None:
-            beta_rate, beta_vq = self.sample_selected_beta_pair(n if self.sample_beta_batch else 1)
+            beta_rate, beta_vq = self.sample_beta_pair(n if self.sample_beta_batch else 1)
+        self.last_beta_rate, self.last_beta_vq = beta_rate, beta_vq
         # ---------------------------------------------------------------- train G
         self.g_group.zero_grad()
         ctx = Ctx([self.g_group])                      # D's parameters receive no gradient here (requires_grad_(False), :146)

@@ -12,7 +12,11 @@ all-reduces of the flat gradient buffers (the reference is single-GPU, README.md
 or seeded synthetic tensors.  Checkpoints use the reference's file format: `comp_model_iterXXXXXXX.pth.tar` =
 {'iter', 'comp_model': state_dict}, `discriminator_iter...` = {'iter', 'discriminator': state_dict} (model_saver.py:39-46).
 The optimizer / loss settings are the YAML's `optim` / `loss` sections when present (config/exp1_stage1_3.yaml:43-79), else
-their stage-3 values (g_scheduler and d_scheduler milestones are read separately).  LPIPS: pass --lpips_path (a torch.save'd state
+their stage-3 values (g_scheduler and d_scheduler milestones are read separately).  Every `loss` entry's `type` and keywords are
+honoured or refused before any GPU work (dc_vic_amd/train/losses.py read_loss_section: CrossEntropyLoss / FocalCrossEntropyLoss,
+MSELoss normalize_img / mse_scale, VanillaMSELoss reduction, LPIPSLoss alex); rank 0 prints them as `[train] losses: ...`.
+Without `model.use_selected_beta_pairs` (config/exp1_stage1_3.yaml) beta_rate and beta_vq are drawn per sample from the
+(num_beta_levels + 1)-point grids; `trainer.beta_policy` / `trainer.beta_offset` are read by no GAN trainer of the reference and ignored.  LPIPS: pass --lpips_path (a torch.save'd state
 dict of lpips.LPIPS(net='alex'), loaded with weights_only=True); its weights cannot be fetched offline, so without it a positive
 perceptual weight is an ERROR unless --allow_synthetic_lpips opts into synthetic AlexNet weights (benchmarks / plumbing only).
 --save_step also writes training_state_iter*.pth.tar (Adam moments, step counts, scheduler epochs, beta-sampler RNG; the
@@ -42,6 +46,7 @@ from dc_vic_amd import BaseConfig, build_comp_model  # noqa: E402
 from dc_vic_amd.parallel import launched_by_a_launcher, pin_rank_cpus, self_launch  # noqa: E402
 from dc_vic_amd.registry import TRAINER_REGISTRY  # noqa: E402
 from dc_vic_amd.train import DualBetaCondTamingNLayerDiscriminator  # noqa: E402  (registers both stage-3 trainers)
+from dc_vic_amd.train.losses import build_code_ce_loss, read_loss_section  # noqa: E402
 from dc_vic_amd.train.validation import EvalCSV, eval_image_paths, load_eval_images  # noqa: E402
 
 
@@ -163,7 +168,9 @@ def main():
     p.add_argument("-e", "--eval_step", type=int, default=None, help="validate every N iterations (overrides the YAML's eval_step; 0 = off)")
     p.add_argument("--gan", choices=("vanilla", "oasis"), default=None, help="GAN loss / trainer (default: from the YAML, see choose_gan_trainer)")
     a = p.parse_args()
-    gan_kind, trainer_name, gan_reason = choose_gan_trainer(BaseConfig.fromfile(a.config_path, {"is_train": True}), a.gan)   # before any GPU work
+    opt0 = BaseConfig.fromfile(a.config_path, {"is_train": True})
+    gan_kind, trainer_name, gan_reason = choose_gan_trainer(opt0, a.gan)   # before any GPU work
+    losses = read_loss_section(opt0)                                       # likewise: every `loss` entry is honoured or refused
     if a.eval_dataset_root is not None:
         try:                                          # a folder named on the command line must hold PNGs: checked before any GPU work
             eval_image_paths(a.eval_dataset_root)
@@ -207,12 +214,7 @@ def main():
     dopt.pop("type", None)
     torch.manual_seed(a.seed)                       # identical D initialisation on every rank
     D = DualBetaCondTamingNLayerDiscriminator(**dopt).to(device)
-    lw = {}
-    for name, key in (("distortion", "distortion_loss"), ("perceptual", "perceptual_loss"), ("gan", "gan_loss"),
-                      ("code_distortion", "code_distortion_loss"), ("code_ce", "code_ce_loss")):
-        v = _get(opt, "loss", key, "loss_weight")
-        if v is not None:
-            lw[name] = float(v)
+    lw = dict(losses["weights"])
     from dc_vic_amd.train.trainer import DEFAULT_LOSS
     w_perc = lw.get("perceptual", DEFAULT_LOSS["perceptual"])
     lpips_state = None
@@ -229,13 +231,15 @@ def main():
         w_src = "loss.gan_loss.loss_weight" if "gan" in lw else "default, no reference YAML pins it" if gan_kind == "oasis" else "default"
         print(f"[train] GAN trainer: {gan_kind} ({trainer_name}), chosen by {gan_reason}; generator-side gan weight "
               f"{lw.get('gan', DEFAULT_LOSS['gan']):g} ({w_src})", flush=True)
+        print("[train] losses: " + losses["line"] + "; weights " + ", ".join(f"{k} {lw.get(k, v):g}" for k, v in DEFAULT_LOSS.items()), flush=True)
     trainer = TRAINER_REGISTRY.get(trainer_name)(
         model, D, lr_g=float(_get(opt, "optim", "g_optimizer", "lr", default=1e-4)), lr_d=float(_get(opt, "optim", "d_optimizer", "lr", default=1e-4)),
         milestones=list(_get(opt, "optim", "g_scheduler", "milestones", default=[300000])), gamma=float(_get(opt, "optim", "g_scheduler", "gamma", default=0.1)),
         clip_max_norm=_get(opt, "optim", "clip_max_norm", default=1.0), loss_weights=lw,
         sample_beta_batch=bool(_get(opt, "trainer", "sample_beta_batch", default=True)), dist=dist, seed=a.seed * 100 + rank,
         d_milestones=_get(opt, "optim", "d_scheduler", "milestones", default=None), d_gamma=_get(opt, "optim", "d_scheduler", "gamma", default=None),
-        lpips_state=lpips_state)
+        lpips_state=lpips_state, code_ce_loss=build_code_ce_loss(losses["code_ce"], lw.get("code_ce", DEFAULT_LOSS["code_ce"])),
+        distortion_factor=losses["distortion_factor"], code_distortion_reduction=losses["code_distortion_reduction"])
     start_iter = 0
     if a.resume:
         # base_trainer.py:178-214: comp_model / discriminator / training_state files of one iteration

@@ -87,7 +87,7 @@ SIGNATURES = {
     "dcvic_adam_step_f32": "i:ppppqffffipp", "dcvic_clip_scale_f32": "i:pfpp",
     "dcvic_resample2_f32": "i:ippqiip", "dcvic_s2d_f32": "i:ppqiiiiiiip", "dcvic_maxpool3s2_f32": "i:pppppqiip",
     "dcvic_lpips_tap_f32": "i:pppppiiifp",
-    # OASIS GAN loss (csrc/oasis.hip)
+    # OASIS GAN loss (csrc/chan_ce.hip)
     "dcvic_oasis_ce_workspace_doubles": "q:ii", "dcvic_oasis_ce_f32": "i:ppidppppiiip",
     # full-reference metrics (csrc/metrics.hip)
     "dcvic_l2pool_f32": "i:ppqiip", "dcvic_pair_moments_workspace_doubles": "q:qq", "dcvic_pair_moments_f64": "i:ppiiqpqpp",
@@ -99,7 +99,7 @@ SIGNATURES = {
     "dcvic_msssim_workspace_bytes": "q:iiii", "dcvic_msssim_psnr_f64": "i:ppiiiippppqp",
 }
 SYMBOLS = list(SIGNATURES)
-# include/dcvic_loss.h: the loss entry points declared outside dcvic.h's frozen table, in the same notation (csrc/focal.hip)
+# include/dcvic_loss.h: the loss entry points declared outside dcvic.h's frozen table, in the same notation (csrc/chan_ce.hip)
 LOSS_SIGNATURES = {
     "dcvic_focal_ce_workspace_doubles": "q:ii", "dcvic_focal_ce_f32": "i:ppddpppiiip",
 }

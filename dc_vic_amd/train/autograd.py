@@ -472,7 +472,7 @@ def cross_entropy_loss(ctx: Ctx, logits: Var, target: Tensor, weight: float) -> 
 
 def focal_cross_entropy_loss(ctx: Ctx, logits: Var, target: Tensor, weight: float, gamma: float, reduction: str = "mean") -> Tensor:
     """weight * reduce((1 - p_t)^gamma * CrossEntropy(logits [N, C, H, W], target [N, H, W])) with reduce = mean over N*H*W or sum
-    (cross_entropy_loss.py:33-53): value and gradient from one pass of csrc/focal.hip; the gradient is seeded into `logits`."""
+    (cross_entropy_loss.py:33-53): value and gradient from one pass of csrc/chan_ce.hip; the gradient is seeded into `logits`."""
     if reduction not in ("mean", "sum"):
         raise ValueError(f"focal_cross_entropy_loss: reduction {reduction!r}, expected 'mean' or 'sum'")
     ld = _dense(logits.data)
@@ -485,7 +485,7 @@ def focal_cross_entropy_loss(ctx: Ctx, logits: Var, target: Tensor, weight: floa
 
 def oasis_gan_loss(ctx: Ctx, logits: Var, target: Tensor, is_real: bool, weight: float, want_score: bool = False):
     """weight * CrossEntropy(logits [N, C, H, W], target + 1 if is_real else 0), mean over N*H*W (src/losses/oasis_gan_loss.py:40-79):
-    value, gradient and -- with want_score -- mean(logits[:, 1:]) from one pass of csrc/oasis.hip.  Returns the value, or
+    value, gradient and -- with want_score -- mean(logits[:, 1:]) from one pass of csrc/chan_ce.hip.  Returns the value, or
     (value, score) with want_score; the gradient is seeded into `logits`."""
     ld = _dense(logits.data)
     N, Cc, H, W = ld.shape

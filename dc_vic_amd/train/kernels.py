@@ -128,35 +128,34 @@ def cross_entropy(logits: Tensor, target: Tensor, w: float, want_grad: bool = Tr
     return nll, dl
 
 
-def oasis_ce(logits: Tensor, target: Optional[Tensor], is_real: bool, scale: float, want_grad: bool = True, want_score: bool = False):
-    """OASIS GAN loss (csrc/oasis.hip) in one pass over logits [N, C, H, W]: (loss, dlogits or None, score or None) with
-    loss = scale * sum_positions CE(logits, index + 1 if is_real else 0), dlogits its gradient and score = mean(logits[:, 1:])."""
+def _chan_ce_buffers(name: str, ws_doubles, logits: Tensor, target: Optional[Tensor], want_grad: bool):
+    """What oasis_ce and focal_ce share: the operand checks, then (N, C, HW, workspace sized by the entry point's query `ws_doubles`,
+    loss, dlogits or None)."""
     if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("oasis_ce: contiguous fp32 logits [N, C, H, W]")
+        raise ValueError(f"{name}: contiguous fp32 logits [N, C, H, W]")
     N, Cc, H, W = logits.shape
     if target is not None and (target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != N * H * W):
-        raise ValueError(f"oasis_ce: contiguous int64 targets with {N * H * W} elements")
-    ws = _workspace(int(lib().dcvic_oasis_ce_workspace_doubles(N, H * W)), logits.device, "oasis_ws", torch.float64)
+        raise ValueError(f"{name}: contiguous int64 targets with {N * H * W} elements")
+    ws = _workspace(int(ws_doubles(N, H * W)), logits.device, name, torch.float64)
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-    dl = torch.empty_like(logits) if want_grad else None
+    return N, Cc, H * W, ws, loss, torch.empty_like(logits) if want_grad else None
+
+
+def oasis_ce(logits: Tensor, target: Optional[Tensor], is_real: bool, scale: float, want_grad: bool = True, want_score: bool = False):
+    """OASIS GAN loss (csrc/chan_ce.hip) in one pass over logits [N, C, H, W]: (loss, dlogits or None, score or None) with
+    loss = scale * sum_positions CE(logits, index + 1 if is_real else 0), dlogits its gradient and score = mean(logits[:, 1:])."""
+    N, Cc, HW, ws, loss, dl = _chan_ce_buffers("oasis_ce", lib().dcvic_oasis_ce_workspace_doubles, logits, target, want_grad)
     score = torch.empty(1, dtype=torch.float32, device=logits.device) if want_score else None
-    check(lib().dcvic_oasis_ce_f32(_p(logits), _p(target), 1 if is_real else 0, scale, _p(loss), _p(dl), _p(score), _p(ws), N, Cc, H * W,
+    check(lib().dcvic_oasis_ce_f32(_p(logits), _p(target), 1 if is_real else 0, scale, _p(loss), _p(dl), _p(score), _p(ws), N, Cc, HW,
                                    _stream()), "oasis_ce")
     return loss, dl, score
 
 
 def focal_ce(logits: Tensor, target: Tensor, gamma: float, scale: float, want_grad: bool = True):
-    """Focal cross entropy (csrc/focal.hip) in one pass over logits [N, C, H, W]: (loss, dlogits or None) with
+    """Focal cross entropy (csrc/chan_ce.hip) in one pass over logits [N, C, H, W]: (loss, dlogits or None) with
     loss = scale * sum_positions (1 - p_t)^gamma * CE(logits, target) and dlogits its gradient; gamma is 0 or >= 1."""
-    if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("focal_ce: contiguous fp32 logits [N, C, H, W]")
-    N, Cc, H, W = logits.shape
-    if target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != N * H * W:
-        raise ValueError(f"focal_ce: contiguous int64 targets with {N * H * W} elements")
-    ws = _workspace(int(lib().dcvic_focal_ce_workspace_doubles(N, H * W)), logits.device, "focal_ws", torch.float64)
-    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-    dl = torch.empty_like(logits) if want_grad else None
-    check(lib().dcvic_focal_ce_f32(_p(logits), _p(target), float(gamma), scale, _p(loss), _p(dl), _p(ws), N, Cc, H * W, _stream()), "focal_ce")
+    N, Cc, HW, ws, loss, dl = _chan_ce_buffers("focal_ce", lib().dcvic_focal_ce_workspace_doubles, logits, target, want_grad)
+    check(lib().dcvic_focal_ce_f32(_p(logits), _p(target), float(gamma), scale, _p(loss), _p(dl), _p(ws), N, Cc, HW, _stream()), "focal_ce")
     return loss, dl
 
 

@@ -41,7 +41,7 @@ class CrossEntropyLoss:
 
 @LOSS_REGISTRY.register()
 class FocalCrossEntropyLoss:
-    """cross_entropy_loss.py:32-53: loss_weight * reduce((1 - p_t)^gamma * CE) with reduction mean or sum, one pass of csrc/focal.hip.
+    """cross_entropy_loss.py:32-53: loss_weight * reduce((1 - p_t)^gamma * CE) with reduction mean or sum, one pass of csrc/chan_ce.hip.
     `reduction: none` returns a per-position map for the per-sample beta weighting of the rate-distortion trainers, which are not
     built; the reference forwards further keywords to nn.CrossEntropyLoss, none of which is built either."""
 

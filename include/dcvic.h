@@ -383,7 +383,7 @@ int dcvic_reduce_loss_f32(int kind, const float* a, const float* b, long long le
                           double* workspace, void* stream);
 /* Cross entropy over the channel axis (src/losses/cross_entropy_loss.py): per-pixel nll and dlogits = w * (softmax - onehot). */
 int dcvic_cross_entropy_f32(const float* logits, const int64_t* target, float* nll, float* dlogits, int N, int C, int HW, float w, void* stream);
-/* OASIS GAN loss (src/losses/oasis_gan_loss.py; csrc/oasis.hip) on logits [N][C][HW] (fp32, dense) and int64 VQ indices [N][HW]:
+/* OASIS GAN loss (src/losses/oasis_gan_loss.py; csrc/chan_ce.hip) on logits [N][C][HW] (fp32, dense) and int64 VQ indices [N][HW]:
  * the class per position is index + 1 when is_real, else 0 (target may be NULL then); needs C >= 2 and index + 1 < C (an index
  * outside that range makes the loss NaN, it is never used as an address).
  *   loss[0]  = scale * sum_positions (logsumexp_c - logit[class])      (fp64 sum in a fixed order; the caller passes weight / (N*HW))

@@ -14,7 +14,7 @@ extern "C" {
 #endif
 
 /* Focal cross entropy over the channel axis (src/losses/cross_entropy_loss.py:33-53 `FocalCrossEntropyLoss.forward`;
- * csrc/focal.hip) on logits [N][C][HW] (fp32, dense) and int64 classes [N][HW].  Per position
+ * csrc/chan_ce.hip) on logits [N][C][HW] (fp32, dense) and int64 classes [N][HW].  Per position
  *   ce = logsumexp_c(z) - z[t],  p_t = exp(-ce),  q = 1 - p_t,  f = q^gamma * ce
  *   loss[0] = scale * sum_positions f      (the caller passes weight / (N*HW) for reduction "mean", weight for "sum")
  *   dlogits[j] = scale * (p_j - [j == t]) * (q^gamma + gamma * q^(gamma-1) * p_t * ce), or NULL for the value only

@@ -1,4 +1,4 @@
-"""Stage 1-3 training on a real MI355X: the focal cross-entropy kernel (csrc/focal.hip) against torch fp64 autograd of the
+"""Stage 1-3 training on a real MI355X: the focal cross-entropy kernel (csrc/chan_ce.hip) against torch fp64 autograd of the
 reference expression, its bits, a target outside the classes, the reference's own FocalCrossEntropyLoss (tests/golden/focal.npz),
 the tape op, and the trainer with the beta grid sampler and the focal code loss."""
 import ctypes as C
@@ -122,6 +122,22 @@ def test_focal_ce_is_bit_reproducible_and_ignores_buffer_contents():
         check(lib().dcvic_focal_ce_f32(_p(ld), _p(td), C.c_double(2.0), C.c_double(scale), _p(loss), _p(dl), _p(ws), N, Cc, H * W, _stream()), "focal_ce")
         assert torch.equal(loss, a[0]) and torch.equal(dl, a[1])
         assert not torch.isnan(ws).any()
+
+
+@pytest.mark.parametrize("shape", [(3, 5, 7, 11), (2, 272, 9, 9), (2, 273, 9, 9)], ids=["ragged, C < waves", "last cached C", "first streaming C"])
+def test_focal_gamma0_and_oasis_real_share_one_core(shape):
+    """The two entry points are one kernel template: focal at gamma 0 on the classes idx + 1 and OASIS (real) on the indices idx
+    return the same bits, value and gradient."""
+    from dc_vic_amd.train import kernels as K
+    N, Cc, H, W = shape
+    ld = (rnd(N, Cc, H, W, seed=340 + Cc) * 2).to(DEV)
+    idx = torch.randint(0, Cc - 1, (N, H, W), generator=torch.Generator().manual_seed(341))
+    idx.view(-1)[0], idx.view(-1)[-1] = 0, Cc - 2
+    td = idx.to(DEV)
+    s = 0.5 / (N * H * W)
+    fl, fg = K.focal_ce(ld, td + 1, 0.0, s, want_grad=True)
+    ol, og, _ = K.oasis_ce(ld, td, True, s, want_grad=True)
+    assert torch.isfinite(fl).all() and torch.equal(fl, ol) and torch.equal(fg, og)
 
 
 @pytest.mark.parametrize("bad", [-1, None], ids=["-1", "C"])

@@ -1,4 +1,4 @@
-"""OASIS GAN training on a real MI355X: the loss kernel (csrc/oasis.hip) against an fp64 restatement, its determinism and
+"""OASIS GAN training on a real MI355X: the loss kernel (csrc/chan_ce.hip) against an fp64 restatement, its determinism and
 argument checks, the 257-class discriminator + loss against the reference's own modules (tests/golden/oasis.npz), the 512 -> 257
 convolution's gradients, one full G + D step against torch autograd over the CPU oracle, and the CLI with --resume."""
 import json

@@ -131,6 +131,43 @@ int dcvic_conv_tiles(const char* name, ConvKArgs* K, int kc, int co, int th, int
 // defined in conv.hip.  Grid of a persistent kernel: one workgroup per CU, a multiple of the 8 XCDs, no more than nblocks needs.
 int dcvic_persistent_grid(long long nblocks);
 
+// ---- host side of the four Winograd kernels (wino.hip, wino44.hip, wino44_ups.hip)
+// Their packed weights are [co-tile of `co` output channels][chunk of `kc` input channels][`us` floats: the stage's slab].
+struct DcvicWinoPack { int co, kc, us; };
+static inline size_t dcvic_wino_packed_bytes(const DcvicWinoPack& p, int Cin, int Cout) {
+    if (Cin <= 0 || Cout <= 0) return 0;
+    return (size_t)((Cout + p.co - 1) / p.co) * ((Cin + p.kc - 1) / p.kc) * p.us * sizeof(float);
+}
+// one thread per packed float: kern(w, packed, Cin, Cout, n_chunks, total)
+static inline int dcvic_wino_pack(const char* name, void (*kern)(const float*, float*, int, int, int, long long), const DcvicWinoPack& p,
+                                  const float* w, float* packed, int Cin, int Cout, void* stream) {
+    DCVIC_CHECK_ARG(w && packed && Cin > 0 && Cout > 0, "%s: bad argument", name);
+    const int n_chunks = (Cin + p.kc - 1) / p.kc;
+    const long long total = (long long)((Cout + p.co - 1) / p.co) * n_chunks * p.us;
+    kern<<<dcvic_cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(w, packed, Cin, Cout, n_chunks, total);
+    DCVIC_CHECK_LAUNCH(name);
+    return DCVIC_OK;
+}
+// io check of a Winograd entry point `name`: 1..3 sources in multiples of a chunk, 16-byte views (the input is staged in 16-byte LDS-DMA
+// segments), plane limit H x W x 8 < 2^31, no affine / init.  out_geom: DCVIC_OUT_SAME or DCVIC_OUT_X2 (nearest-x2 upsample first).
+static inline int dcvic_wino_check(const char* name, int out_geom, const DcvicWinoPack& p, int Cin, int Cout, const float* packed, const dcvic_conv_io* io, ConvKArgs* K) {
+    const DcvicConvRules rules = {name, Cin, Cout, DCVIC_MAX_SRC, p.kc, true, out_geom, false, false, 1ll << 28};
+    if (const int rc = dcvic_conv_check_io(rules, packed, io, K)) return rc;
+    DCVIC_CHECK_ARG((io->W & 3) == 0, "%s: %swidth must be a multiple of 4", name, out_geom == DCVIC_OUT_X2 ? "input " : "");
+    return DCVIC_OK;
+}
+// tiles of th x tw output pixels x `co` channels, then KERN on the persistent grid (one workgroup per CU walks its share of the tiles)
+template <void (*KERN)(ConvKArgs)>
+static int dcvic_wino_run(const char* name, ConvKArgs* K, const DcvicWinoPack& p, int th, int tw, int threads, size_t lds_bytes, void* stream) {
+    if (const int rc = dcvic_conv_tiles(name, K, p.kc, p.co, th, tw)) return rc;
+    static std::atomic<unsigned> attr_mask{0};
+    if (DcvicAttrOnce once_{attr_mask})
+        hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    KERN<<<dcvic_persistent_grid(K->nblocks), threads, lds_bytes, (hipStream_t)stream>>>(*K);
+    DCVIC_CHECK_LAUNCH(name);
+    return DCVIC_OK;
+}
+
 // defined in conv3x3.hip: returns DCVIC_OK after launching, or 1 if the layer is not eligible
 int dcvic_try_conv3x3_dma(const ConvKArgs& K, int n_src, bool upsample, int cls, hipStream_t st, int* variant_out);
 

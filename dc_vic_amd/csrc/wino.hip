@@ -27,15 +27,8 @@
 //     between horizontally adjacent tiles).
 // LDS: 2 x 13 KiB raw patch + 2 x 32 KiB U + 2 x 32 KiB V + two bias rows = 154.5 KiB: one workgroup per CU.
 // Deterministic and batch-invariant: per position the reduction runs over chunks ascending, then k-steps ascending inside
-// the MFMA's ordered fmaf chain; the tiling never depends on N.  Build log, measurements and the timing experiments behind the
-// DBG / RS template paths: profiles/r2_wino_experiments.md.
-#include "conv_common.h"
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ float dcvic_wino_zero[16];   // zero-initialised: source of padded lanes
+// the MFMA's ordered fmaf chain; the tiling never depends on N.  Build log and measurements: profiles/r2_wino_experiments.md.
+#include "wino_stream.h"
 
 #define WN_TH 8
 #define WN_TW 32
@@ -85,15 +78,6 @@ __global__ void wino_pack_kernel(const float* __restrict__ w, float* __restrict_
     wp[i] = v;
 }
 
-// DBG: timing experiments with WRONG results, instantiated only in the diagnostic build (-DDCVIC_WINO_EXPERIMENTS,
-// tools/build_wino_experiments.sh -> tools/libdcvic_wino_exp.so, never in libdcvic_hip.so), selected by DCVIC_WINO_DEBUG=16*DBG: 1 no stage barrier, 2 no transform, 4 no DMA, 8 no operand waits,
-// 16 no X DMA, 32 no U DMA, 64 no vmcnt wait in front of the stage barrier
-#ifdef DCVIC_WINO_EXPERIMENTS
-#define WN_DBG_ARG(bit) (K.TG & (bit))     // 1: every X load from the cached zero source, 2: the same U slab every stage
-#else
-#define WN_DBG_ARG(bit) false
-#endif
-template <int DBG>
 __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_kernel(const ConvKArgs K) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
@@ -101,72 +85,26 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_kernel(const ConvK
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // 0..7
 
     const long long HW = (long long)K.H * K.W;
-    const int S = K.n_chunks;                                     // stages (8-channel chunks) per tile
-    const long long x_stride = (long long)KC * HW;                // floats between two stages of one source
 
-    // ---- PERSISTENT workgroup: XCD x = blockIdx.x % 8 owns the contiguous range [xs, xe) of tile indices (cotile fastest, so
-    // the workgroups of one L2 share input patches and weight slabs); slot j = blockIdx.x / 8 takes tiles xs + j, xs + j + J, ...
-    // All stages of all its tiles form ONE stream: the DMA of the next tile's first stages is in flight during the last stages
-    // and the (register-only) epilogue of the current tile, so nothing drains at a tile boundary.
-    int xe;
-    const int J = (int)gridDim.x / NXCD;
-    int first;
-    {
-        const int nb = K.nblocks, q = nb / NXCD, r = nb % NXCD, x = (int)blockIdx.x % NXCD;
-        const int xs = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        xe = xs + (x < r ? q + 1 : q);
-        first = xs + (int)blockIdx.x / NXCD;
-    }
-    if (first >= xe) return;                                      // (uniform: the whole workgroup leaves before any barrier)
-    const int ntile = (xe - first + J - 1) / J;
-    const int total = ntile * S;
-    auto decode = [&](int b, int& cotile, int& n, int& oy0, int& ox0) __attribute__((always_inline)) {
-        cotile = b % K.n_cotiles; b /= K.n_cotiles;
-        const int tile_x = b % K.tiles_x; b /= K.tiles_x;
-        const int tile_y = b % K.tiles_y; b /= K.tiles_y;
-        n = b; oy0 = tile_y * WN_TH; ox0 = tile_x * WN_TW;
-    };
-
-    // ---- raw-patch DMA: element e = tid + s*512 of [8 ch][10][34]; running pointers, advanced per stage, re-derived per tile
-    const float* xp[WN_XSLOTS];
-    int poff[WN_XSLOTS];
-    int x_left = 0, x_n = 0, x_b = first, x_next = 0;             // X stream: image, tile index, chunk inside the tile
-    auto x_rebase = [&](int c) __attribute__((always_inline)) {                                  // pointers for absolute input channel c of image x_n
-        int si = 0;
-        if (c >= K.srcC[0]) { c -= K.srcC[0]; si = 1; if (c >= K.srcC[1]) { c -= K.srcC[1]; si = 2; } }
-        const float* base = K.src[si] + (long long)x_n * K.src_bs[si] + (long long)c * HW;
-#pragma unroll
-        for (int s = 0; s < WN_XSLOTS; ++s) xp[s] = (poff[s] >= 0 && !WN_DBG_ARG(1)) ? base + poff[s] : dcvic_wino_zero;
-        x_left = K.srcC[si] - c;
-    };
-    auto x_setup = [&](int b) __attribute__((always_inline)) {
-        int cot, oy0, ox0;
-        decode(b, cot, x_n, oy0, ox0);
-        const int iy0 = oy0 - 1, ix0 = ox0 - 1;
-#pragma unroll
-        for (int s = 0; s < WN_XSLOTS; ++s) {
-            const int e = tid + s * WN_THREADS;                    // float4 segment e of [8 ch][10 rows][10 segments]
-            int o = -1;
-            if (e < WN_SEGS) {
-                const int k = e / WN_PSEGS, r = e - k * WN_PSEGS;  // (r >= 100: the plane's two padding segments, fed from the zero word)
-                const int py = r / 10, seg = r - py * 10;
-                const int iy = iy0 + py, ix = ix0 - 3 + 4 * seg;   // W % 4 == 0: a segment is entirely inside or outside the row
-                if (r < 100 && iy >= 0 && iy < K.H && ix >= 0 && ix < K.W) o = (int)(k * HW) + iy * K.W + ix;
-            }
-            poff[s] = o;
+    // ---- the workgroup's stage stream (wino_stream.h), tile index co-tile fastest
+    using Tiles = WinoTiles<true, WN_TH, WN_TW>;
+    const Tiles T(K, tid);
+    if (T.empty()) return;
+    const int total = T.total;
+    // ---- raw-patch DMA: float4 segment e = tid + s*512 of [8 ch][10 rows][10 segments] (+ 2 padding segments per plane, fed from the zero word)
+    auto X = wino_x_stream<WN_XSLOTS, WN_THREADS, KC>(T, HW, [&](int e, int oy0, int ox0) __attribute__((always_inline)) {
+        int o = -1;
+        if (e < WN_SEGS) {
+            const int k = e / WN_PSEGS, r = e - k * WN_PSEGS;
+            const int py = r / 10, seg = r - py * 10;
+            const int iy = oy0 - 1 + py, ix = ox0 - 4 + 4 * seg;       // W % 4 == 0: a segment is entirely inside or outside the row
+            if (r < 100 && iy >= 0 && iy < K.H && ix >= 0 && ix < K.W) o = (int)(k * HW) + iy * K.W + ix;
         }
-        x_rebase(0);
-    };
-    x_setup(first);
+        return o;
+    });
     // ---- weight DMA: the stage's 32 KiB slab is already the LDS image; thread moves float4 #(tid + j*512)
-    const float* wp0;                                             // the stage's slab (UNIFORM: scalar base + 32-bit lane offset -> saddr form of the DMA)
+    WinoUStream<WN_US, Tiles> U(T);
     const unsigned u_lane = 16u * (unsigned)tid;                  // this thread's first float4, in bytes
-    int u_b = first, u_next = 0;                                  // U stream
-    auto u_setup = [&](int b) __attribute__((always_inline)) {
-        const float* wbase = K.wp + (long long)(b % K.n_cotiles) * S * (long long)WN_US;
-        wp0 = wbase;
-    };
-    u_setup(first);
     // ---- input transform: this thread's (channel, tile) of a stage
     //   wave -> (th, k); lane -> (n, ks, blk);  channel 4ks + k, tile row 2th + blk, tile column n.
     //   The patch's four columns 2n + 3 .. 2n + 6 start on an ODD dword (16-byte DMA segments of a pad-1 convolution), so dword reads
@@ -191,12 +129,8 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_kernel(const ConvK
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
 
-    // All LDS traffic of the loop is inline asm with hand-placed `s_waitcnt lgkmcnt(0)`: hipcc guards every LDS access it
-    // can see with `s_waitcnt vmcnt(0)` while an LDS-DMA is in flight (it cannot prove the DMA's destination does not alias),
-    // which serialises the stage into "DMA latency + transform + MFMA" (measured: 52 % -> MFMA-busy).  Nothing below is
-    // visible to it as an LDS access, so the only vmcnt wait is the explicit one in front of the stage barrier.
-#define WN_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define WN_WAIT_LDS() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); WN_FENCE(); } while (0)
+    // All LDS traffic of the loop is inline asm with hand-placed waits (wino_stream.h), so the only vmcnt wait is the explicit one in
+    // front of the stage barrier.
     // raw 4x4 patch of the transform.  The asm loads write the very variables t_compute reads after the wait: a copy made
     // between a load and the `s_waitcnt` would read the register before the LDS data has landed.
     f32x2 tp0[4], tp1[4], tp2[4];                                 // row r: dwords (2n+2, 2n+3) | (2n+4, 2n+5) | (2n+6, 2n+7); the patch is the middle four
@@ -240,98 +174,34 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_kernel(const ConvK
     auto dma_x = [&](auto s_, int buf) {
         constexpr int sl = decltype(s_)::value;
         if (sl == 0 || wave < 5)                                  // (wave-uniform: segments 512 .. 799 live in waves 0 .. 4 of slot 1)
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const float4*>(xp[sl]), (lds_ptr_t)(smem + buf * WN_XS + (wave * 64 + sl * WN_THREADS) * 4), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const float4*>(X.xp[sl]), (lds_ptr_t)(smem + buf * WN_XS + (wave * 64 + sl * WN_THREADS) * 4), 16, 0, 0);
     };
     auto dma_u = [&](auto j_, int buf) {
         constexpr int j = decltype(j_)::value;
-        {   // saddr form by hand (hipcc re-materialises 64-bit per-lane addresses inside the loop): scalar base + 32-bit lane offset
-            // instead of a 64-bit address per lane -- 2.38 -> 2.32 ms on the 256 -> 256 @ 128^2 x 32 layer
-            const unsigned voff = u_lane + 16u * WN_THREADS * j;
-            const unsigned long long sb = (unsigned long long)__builtin_amdgcn_readfirstlane((int)(reinterpret_cast<unsigned long long>(wp0) & 0xffffffffull)) & 0xffffffffull
-                                        | ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(reinterpret_cast<unsigned long long>(wp0) >> 32)) << 32);
-            const unsigned lds = (unsigned)(4 * (WN_OFF_U + buf * WN_US + (wave * 64 + j * WN_THREADS) * 4));
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sb), "s"(lds) : "memory", "m0");
-        }
-    };
-    // RS (DBG bit 256) = REGISTER STAGING instead of LDS-DMA: the stage's U slab and X patch are fetched into 24 registers by plain
-    // 16-byte global loads one stage earlier and written to LDS with ds_write_b128 (an LDS-DMA piece holds the SIMD's vector issue
-    // for 60 - 185 cycles, MI355X_MICROARCH "LDS-DMA piece issue cost"; a load + a store are two short instructions that hide
-    // inside MFMA gaps).  Loads are ordinary C++ loads: hipcc places the counted vmcnt waits in front of the stores itself.
-    constexpr bool RS = (DBG & 256) != 0;
-    f32x4 su[4], sx[2];
-    const unsigned st_base = 16u * (unsigned)tid;
-    auto ld_u = [&](auto j_) {
-        constexpr int j = decltype(j_)::value;
-        su[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(wp0) + (size_t)(u_lane + 16u * WN_THREADS * j));
-    };
-    auto st_u = [&](auto j_, int buf) {
-        constexpr int j = decltype(j_)::value;
-        const f32x4 v = su[j];
-        const unsigned a = st_base + 4u * (unsigned)(WN_OFF_U + buf * WN_US);
-        asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(a), "v"(v), "n"(16 * WN_THREADS * j) : "memory");
-    };
-    auto ld_x = [&](auto s_) {
-        constexpr int sl = decltype(s_)::value;
-        if (sl == 0 || wave < 5) sx[sl] = *reinterpret_cast<const f32x4*>(xp[sl]);
-    };
-    auto st_x = [&](auto s_, int buf) {
-        constexpr int sl = decltype(s_)::value;
-        if (sl == 0 || wave < 5) {
-            const f32x4 v = sx[sl];
-            const unsigned a = st_base + 4u * (unsigned)(buf * WN_XS);
-            asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(a), "v"(v), "n"(16 * WN_THREADS * sl) : "memory");
-        }
-    };
-    auto x_advance = [&]() __attribute__((always_inline)) {                                     // after the DMA of an X stage: on to the next stage of the stream
-        if (++x_next == S) {
-            x_next = 0;
-            x_b += J;
-            if (x_b < xe) x_setup(x_b);
-        } else {
-            x_left -= KC;
-            if (x_left > 0) {
-#pragma unroll
-                for (int sl = 0; sl < WN_XSLOTS; ++sl) xp[sl] += (poff[sl] >= 0 && !WN_DBG_ARG(1)) ? x_stride : 0ll;   // (padding lanes stay on the zero word)
-            } else {
-                x_rebase(x_next * KC);
-            }
-        }
-    };
-    auto u_advance = [&]() __attribute__((always_inline)) {
-        if (++u_next == S) {
-            u_next = 0;
-            u_b += J;
-            if (u_b < xe) u_setup(u_b);
-        } else {
-            if (!WN_DBG_ARG(2)) wp0 += WN_US;
-        }
+        wino_dma_saddr(U.p, u_lane + 16u * WN_THREADS * j, (unsigned)(4 * (WN_OFF_U + buf * WN_US + (wave * 64 + j * WN_THREADS) * 4)));
     };
 
     // ---- epilogue of one tile, in registers: lane holds element (co = 16cg + 4(lane/16) + r, tile = (row 2th + blk, column
     // lane%16)) of all 16 positions.  A^T M A, bias -> act -> (+res) -> float2 stores; a block's residuals are requested up front.
-    float* const sbias = smem + WN_OFF_BIAS;                      // [2][64], by tile parity
+    WinoTileCursor<WN_CO, Tiles> C(T, smem + WN_OFF_BIAS);        // compute stream: the tile, its bias row in [2][64] by tile parity
     const int tx = lane & 15, lq = lane >> 4;
     const int act = K.act;
-    const bool has_bias = K.bias != nullptr, has_res = K.res != nullptr;
-    auto tile_epilogue = [&](int cotile, int n, int oy0, int ox0, int par) __attribute__((always_inline)) {
-        // Lanes tx and tx ^ 1 hold the 2x2 outputs of two horizontally adjacent tiles: they swap one row each (DPP quad_perm
-        // [1,0,3,2]) so that the even lane owns FOUR consecutive columns of the upper row and the odd lane of the lower row --
-        // one 16-byte store (and residual load) per lane and channel instead of two 8-byte ones (VMEM instructions are the
-        // expensive part of this kernel's side work).
-        const bool odd = tx & 1;
-        const int ox = ox0 + 2 * (tx & ~1);
+    const bool has_res = K.res != nullptr;
+    auto tile_epilogue = [&]() __attribute__((always_inline)) {
+        const bool odd = tx & 1;                                  // (wino22_store: the odd lane of a pair stores the lower row)
+        const int ox = C.ox0 + 2 * (tx & ~1);
         const bool in_x = ox < K.W;                               // W % 4 == 0: all four columns or none
-        const int co0 = cotile * WN_CO + cg * 16 + 4 * lq;
+        const int co0 = C.cotile * WN_CO + cg * 16 + 4 * lq;
         float bv[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) bv[r] = has_bias ? sbias[par * WN_CO + cg * 16 + 4 * lq + r] : 0.f;
+        for (int r = 0; r < 4; ++r) bv[r] = C.bias(cg * 16 + 4 * lq + r);
         dcvic_static_for<0, 2>([&](auto blk_) {
             constexpr int blk = decltype(blk_)::value;
-            const int oy = oy0 + 2 * (2 * th + blk) + (odd ? 1 : 0);
+            const int oy = C.oy0 + 2 * (2 * th + blk) + (odd ? 1 : 0);
             const bool live = in_x && oy < K.H;
             const long long pix = (long long)oy * K.W + ox;
-            float* const ob = K.out + (long long)n * K.out_bs + pix;
-            const float* const rb = has_res ? K.res + (long long)n * K.res_bs + pix : nullptr;
+            float* const ob = K.out + (long long)C.n * K.out_bs + pix;
+            const float* const rb = has_res ? K.res + (long long)C.n * K.res_bs + pix : nullptr;
             f32x4 rv[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -348,13 +218,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_kernel(const ConvK
                 }
                 float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
                 float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
-                y00 = dcvic_act(y00 + bv[r], act); y01 = dcvic_act(y01 + bv[r], act);
-                y10 = dcvic_act(y10 + bv[r], act); y11 = dcvic_act(y11 + bv[r], act);
-                const float g0 = odd ? y00 : y10, g1 = odd ? y01 : y11;            // what the neighbour needs from this lane
-                const float n0 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, g0), 0xB1, 0xF, 0xF, true));
-                const float n1 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, g1), 0xB1, 0xF, 0xF, true));
-                const f32x4 o = odd ? f32x4{n0, n1, y10, y11} : f32x4{y00, y01, n0, n1};
-                if (live && co0 + r < K.Cout) *reinterpret_cast<f32x4*>(ob + (long long)(co0 + r) * HW) = o + rv[r];
+                wino22_store(y00, y01, y10, y11, bv[r], act, odd, rv[r], ob + (long long)(co0 + r) * HW, live && co0 + r < K.Cout);
             }
         });
 #pragma unroll
@@ -364,52 +228,27 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_kernel(const ConvK
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
     };
-    auto stage_bias = [&](int b, int par) __attribute__((always_inline)) {                       // bias row of tile b -> sbias[par] (read >= one barrier later)
-        if (tid < WN_CO) sbias[par * WN_CO + tid] = has_bias ? K.bias[min((b % K.n_cotiles) * WN_CO + tid, K.Cout - 1)] : 0.f;
-    };
 
     // ---- pipeline
-    int c_b = first, c_chunk = 0, c_par = 0;                      // compute stream: tile, chunk inside it, tile parity
-    int c_cotile, c_n, c_oy0, c_ox0;
-    decode(first, c_cotile, c_n, c_oy0, c_ox0);
-    stage_bias(first, 0);
-    if constexpr (RS) {
-        // X(0) -> Xr[0], X(1) -> Xr[1], U(0) -> U[0]; U(1) and X(2) stay in the staging registers for stage 0 to store
-        dcvic_static_for<0, WN_XSLOTS>([&](auto s_) { ld_x(s_); });
-        dcvic_static_for<0, WN_XSLOTS>([&](auto s_) { st_x(s_, 0); });
-        x_advance();
-        if (total > 1) {
-            dcvic_static_for<0, WN_XSLOTS>([&](auto s_) { ld_x(s_); });
-            dcvic_static_for<0, WN_XSLOTS>([&](auto s_) { st_x(s_, 1); });
-            x_advance();
-        }
-        dcvic_static_for<0, 4>([&](auto j_) { ld_u(j_); });
-        dcvic_static_for<0, 4>([&](auto j_) { st_u(j_, 0); });
-        u_advance();
-        if (total > 1) { dcvic_static_for<0, 4>([&](auto j_) { ld_u(j_); }); u_advance(); }
-        if (total > 2) { dcvic_static_for<0, WN_XSLOTS>([&](auto s_) { ld_x(s_); }); x_advance(); }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    } else {
-        dcvic_static_for<0, WN_XSLOTS>([&](auto s_) { dma_x(s_, 0); });
-        x_advance();
-        dcvic_static_for<0, 4>([&](auto j_) { dma_u(j_, 0); });
-        u_advance();
-        if (total > 1) {
-            dcvic_static_for<0, WN_XSLOTS>([&](auto s_) { dma_x(s_, 1); });
-            x_advance();
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dcvic_static_for<0, WN_XSLOTS>([&](auto s_) { dma_x(s_, 0); });
+    X.advance();
+    dcvic_static_for<0, 4>([&](auto j_) { dma_u(j_, 0); });
+    U.advance();
+    if (total > 1) {
+        dcvic_static_for<0, WN_XSLOTS>([&](auto s_) { dma_x(s_, 1); });
+        X.advance();
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    WN_FENCE();
+    WINO_FENCE();
     dcvic_static_for<0, 4>([&](auto r_) { t_load(r_, t_src); });
-    WN_WAIT_LDS();
+    WINO_WAIT_LDS();
     dcvic_static_for<0, 4>([&](auto c_) { t_compute(c_); });
     dcvic_static_for<0, 4>([&](auto a_) { t_rows(a_); });
     dcvic_static_for<0, 8>([&](auto p_) { t_store(p_, t_dst); });
-    WN_WAIT_LDS();
+    WINO_WAIT_LDS();
     __syncthreads();
-    WN_FENCE();
+    WINO_FENCE();
     op_load(std::integral_constant<int, 0>{}, op_u, op_v);        // first operands of stage 0
     // more1 / more2: a stage g + 1 / g + 2 exists in the stream (compile-time: no branches between the MFMAs)
     auto run_stage = [&](auto more1_, auto more2_, int g) __attribute__((always_inline)) {
@@ -427,67 +266,39 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_kernel(const ConvK
         dcvic_static_for<0, 8>([&](auto j_) {
             constexpr int j = decltype(j_)::value;
             if constexpr (j < 7) {
-                if constexpr (!(DBG & 8)) WN_WAIT_LDS();
+                WINO_WAIT_LDS();
                 op_load(std::integral_constant<int, j + 1>{}, ua, va);
             } else {
-                if constexpr ((DBG & 64) || RS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // (RS: nothing lands by DMA)
-                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                if constexpr (!(DBG & 1)) __syncthreads();
-                WN_FENCE();
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                __syncthreads();
+                WINO_FENCE();
                 if constexpr (more1) op_load(std::integral_constant<int, 0>{}, op_u + (unsigned)(nxt * WN_US * 4), op_v + (unsigned)(nxt * WN_VS * 4));
             }
-            WN_FENCE();
+            WINO_FENCE();
             dcvic_static_for<0, 8>([&](auto i_) {
                 constexpr int i = decltype(i_)::value, pq = i >> 2, ks = (i >> 1) & 1, blk = i & 1, pp = 2 * j + pq;
                 acc[pp][blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(opA[j & 1][pq * 2 + ks], opB[j & 1][pq][blk * 2 + ks], acc[pp][blk], 0, 0, 0);
-                WN_FENCE();
+                WINO_FENCE();
                 // slot sl = 8j + i.  DMA pieces one every 4th slot (all eight waves run this schedule in step: ten pieces in ten
                 // consecutive slots put 80 VMEM instructions into the CU's address unit at once and stalled the issuing waves --
                 // measured 16 % of the kernel), U first (needed right after the barrier), then X; transform work after them.
                 constexpr int sl = 8 * j + i;
-                auto fillers = [&]() __attribute__((always_inline)) {
-                    if constexpr (RS) {
-                        // stage g: store U(g+1) / X(g+2) (loaded during stage g-1), then reload the registers with U(g+2) / X(g+3)
-                        if constexpr ((sl & 3) == 1 && sl < 16) {
-                            if constexpr (more1) st_u(std::integral_constant<int, sl / 4>{}, nxt);
-                            if constexpr (more2) ld_u(std::integral_constant<int, sl / 4>{});
-                        }
-                        if constexpr ((sl & 3) == 1 && sl >= 16 && sl < 24) {
-                            if constexpr (more2) st_x(std::integral_constant<int, sl / 4 - 4>{}, cur);
-                            if constexpr (more2) { if (g + 3 < total) ld_x(std::integral_constant<int, sl / 4 - 4>{}); }
-                        }
-                    } else {
-                    if constexpr (!(DBG & 36) && more1 && (sl & 3) == 1 && sl < 16) dma_u(std::integral_constant<int, sl / 4>{}, nxt);
-                    if constexpr (!(DBG & 20) && more2 && (sl & 3) == 1 && sl >= 16 && sl < 24) dma_x(std::integral_constant<int, sl / 4 - 4>{}, cur);
-                    }
-                    if constexpr (!(DBG & 2) && more1 && j == 2 && (i & 3) >= 2) t_load(std::integral_constant<int, (i >> 2) * 2 + (i & 1)>{}, xaddr);
-                    if constexpr (!(DBG & 2) && more1 && j == 3 && (i & 3) >= 2) t_compute(std::integral_constant<int, (i >> 2) * 2 + (i & 1)>{});
-                    if constexpr (!(DBG & 2) && more1 && j == 4 && (i & 3) >= 2) t_rows(std::integral_constant<int, (i >> 2) * 2 + (i & 1)>{});
-                    if constexpr (!(DBG & 2) && more1 && (j == 5 || j == 6) && (i & 1)) t_store(std::integral_constant<int, 4 * (j - 5) + (i >> 1)>{}, vaddr);
-                };
-                if constexpr (DBG & 128) {          // experiment: waves 4..7 do the side work of a SIMD twice, waves 0..3 none
-                    if (wave >= 4) { fillers(); WN_FENCE(); fillers(); }
-                } else {
-                    fillers();
-                }
-                WN_FENCE();
+                if constexpr (more1 && (sl & 3) == 1 && sl < 16) dma_u(std::integral_constant<int, sl / 4>{}, nxt);
+                if constexpr (more2 && (sl & 3) == 1 && sl >= 16 && sl < 24) dma_x(std::integral_constant<int, sl / 4 - 4>{}, cur);
+                if constexpr (more1 && j == 2 && (i & 3) >= 2) t_load(std::integral_constant<int, (i >> 2) * 2 + (i & 1)>{}, xaddr);
+                if constexpr (more1 && j == 3 && (i & 3) >= 2) t_compute(std::integral_constant<int, (i >> 2) * 2 + (i & 1)>{});
+                if constexpr (more1 && j == 4 && (i & 3) >= 2) t_rows(std::integral_constant<int, (i >> 2) * 2 + (i & 1)>{});
+                if constexpr (more1 && (j == 5 || j == 6) && (i & 1)) t_store(std::integral_constant<int, 4 * (j - 5) + (i >> 1)>{}, vaddr);
+                WINO_FENCE();
             });
         });
-        if constexpr (RS) {
-            if constexpr (more2) { u_advance(); if (g + 3 < total) x_advance(); }
-        } else {
-            if constexpr (more2) x_advance();
-            if constexpr (more1) u_advance();
+        if constexpr (more2) X.advance();
+        if constexpr (more1) U.advance();
+        if (C.stage_done()) {                                     // the tile is complete: write it out, move the compute stream on
+            tile_epilogue();
+            C.next_tile();
         }
-        if (++c_chunk == S) {                                     // the tile is complete: write it out, move the compute stream on
-            tile_epilogue(c_cotile, c_n, c_oy0, c_ox0, c_par);
-            c_chunk = 0; c_b += J; c_par ^= 1;
-            if (c_b < xe) {
-                decode(c_b, c_cotile, c_n, c_oy0, c_ox0);
-                stage_bias(c_b, c_par);
-            }
-        }
-        WN_FENCE();
+        WINO_FENCE();
     };
     {
         int g = 0;
@@ -495,8 +306,6 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_kernel(const ConvK
         if (g + 1 < total) { run_stage(std::true_type{}, std::false_type{}, g); ++g; }
         run_stage(std::false_type{}, std::false_type{}, g);
     }
-#undef WN_FENCE
-#undef WN_WAIT_LDS
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -546,55 +355,22 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_ups_kernel(const C
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const long long HW = (long long)K.H * K.W;                    // low-resolution input plane
     const long long HWo = (long long)K.Hfull * K.Wfull;           // output plane
-    const int S = K.n_chunks;
-    const long long x_stride = (long long)KC * HW;
-    int xe, first;
-    const int J = (int)gridDim.x / NXCD;
-    {
-        const int nb = K.nblocks, q = nb / NXCD, r = nb % NXCD, x = (int)blockIdx.x % NXCD;
-        const int xs = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        xe = xs + (x < r ? q + 1 : q);
-        first = xs + (int)blockIdx.x / NXCD;
-    }
-    if (first >= xe) return;
-    const int total = ((xe - first + J - 1) / J) * S;
-    auto decode = [&](int b, int& cotile, int& n, int& oy0, int& ox0) __attribute__((always_inline)) {
-        cotile = b % K.n_cotiles; b /= K.n_cotiles;
-        const int tile_x = b % K.tiles_x; b /= K.tiles_x;
-        const int tile_y = b % K.tiles_y; b /= K.tiles_y;
-        n = b; oy0 = tile_y * WN_TH; ox0 = tile_x * WN_TW;          // OUTPUT coordinates
-    };
+    using Tiles = WinoTiles<true, WN_TH, WN_TW>;                  // (tiles of the OUTPUT)
+    const Tiles T(K, tid);
+    if (T.empty()) return;
+    const int total = T.total;
     // ---- raw low-resolution patch: segment e = tid of [8 ch][6 rows][6 segments] (waves 0..4)
-    const float* xp;
-    int poff;
-    int x_left = 0, x_n = 0, x_b = first, x_next = 0;
-    auto x_rebase = [&](int c) __attribute__((always_inline)) {
-        int si = 0;
-        if (c >= K.srcC[0]) { c -= K.srcC[0]; si = 1; if (c >= K.srcC[1]) { c -= K.srcC[1]; si = 2; } }
-        const float* base = K.src[si] + (long long)x_n * K.src_bs[si] + (long long)c * HW;
-        xp = poff >= 0 ? base + poff : dcvic_wino_zero;
-        x_left = K.srcC[si] - c;
-    };
-    auto x_setup = [&](int b) __attribute__((always_inline)) {
-        int cot, oy0, ox0;
-        decode(b, cot, x_n, oy0, ox0);
+    auto X = wino_x_stream<1, WN_THREADS, KC>(T, HW, [&](int e, int oy0, int ox0) __attribute__((always_inline)) {
         int o = -1;
-        if (tid < WU_SEGS) {
-            const int k = tid / 36, r = tid - k * 36;
+        if (e < WU_SEGS) {
+            const int k = e / 36, r = e - k * 36;
             const int py = r / 6, seg = r - py * 6;
             const int iy = oy0 / 2 - 1 + py, ix = ox0 / 2 - 4 + 4 * seg;
             if (iy >= 0 && iy < K.H && ix >= 0 && ix < K.W) o = (int)(k * HW) + iy * K.W + ix;
         }
-        poff = o;
-        x_rebase(0);
-    };
-    x_setup(first);
-    const float* wp0;
-    int u_b = first, u_next = 0;
-    auto u_setup = [&](int b) __attribute__((always_inline)) {
-        wp0 = K.wp + (long long)(b % K.n_cotiles) * S * (long long)WU_US;      // uniform: the DMA uses the saddr form
-    };
-    u_setup(first);
+        return o;
+    });
+    WinoUStream<WU_US, Tiles> U(T);                               // uniform: the DMA uses the saddr form
     // ---- input transform: wave -> (th, k); lane -> (n, blk, ks); channel 4ks + k, low-resolution pixel (row 2th + blk, column n)
     const int t_th = wave >> 2, t_k = wave & 3;
     const int t_n = lane & 15, t_blk = (lane >> 4) & 1, t_ks = lane >> 5;
@@ -610,8 +386,6 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_ups_kernel(const C
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
-#define WN_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define WN_WAIT_LDS() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); WN_FENCE(); } while (0)
     // (the asm loads write the very variables the transform reads after the wait: a copy made between the load and the
     // `s_waitcnt` would read the register before the LDS data has landed)
     f32x2 tlo[3];
@@ -654,51 +428,31 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_ups_kernel(const C
         if constexpr (2 * j + 1 < WU_NPOS) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(b1) : "v"(va), "n"(4 * 512 * (2 * j + 1)));
     };
     auto dma_x = [&](int buf) {
-        if (wave < 5) __builtin_amdgcn_global_load_lds(reinterpret_cast<const float4*>(xp), (lds_ptr_t)(smem + buf * WN_XS + wave * 64 * 4), 16, 0, 0);
+        if (wave < 5) __builtin_amdgcn_global_load_lds(reinterpret_cast<const float4*>(X.xp[0]), (lds_ptr_t)(smem + buf * WN_XS + wave * 64 * 4), 16, 0, 0);
     };
     auto dma_u = [&](auto j_, int buf) {
         constexpr int j = decltype(j_)::value;
-        if (j < 2 || wave < 4) {
-            const unsigned voff = 16u * (unsigned)tid + 16u * WN_THREADS * j;
-            const unsigned long long sb = (unsigned long long)__builtin_amdgcn_readfirstlane((int)(reinterpret_cast<unsigned long long>(wp0) & 0xffffffffull)) & 0xffffffffull
-                                        | ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(reinterpret_cast<unsigned long long>(wp0) >> 32)) << 32);
-            const unsigned lds = (unsigned)(4 * (WN_OFF_U + buf * WN_US + (wave * 64 + j * WN_THREADS) * 4));
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sb), "s"(lds) : "memory", "m0");
-        }
+        if (j < 2 || wave < 4) wino_dma_saddr(U.p, 16u * (unsigned)tid + 16u * WN_THREADS * j, (unsigned)(4 * (WN_OFF_U + buf * WN_US + (wave * 64 + j * WN_THREADS) * 4)));
     };
-    auto x_advance = [&]() __attribute__((always_inline)) {
-        if (++x_next == S) {
-            x_next = 0; x_b += J;
-            if (x_b < xe) x_setup(x_b);
-        } else {
-            x_left -= KC;
-            if (x_left > 0) xp += poff >= 0 ? x_stride : 0ll;
-            else x_rebase(x_next * KC);
-        }
-    };
-    auto u_advance = [&]() __attribute__((always_inline)) {
-        if (++u_next == S) { u_next = 0; u_b += J; if (u_b < xe) u_setup(u_b); }
-        else wp0 += WU_US;
-    };
-    float* const sbias = smem + WN_OFF_BIAS;
+    WinoTileCursor<WN_CO, Tiles> C(T, smem + WN_OFF_BIAS);
     const int tx = lane & 15, lq = lane >> 4;
     const int act = K.act;
-    const bool has_bias = K.bias != nullptr, has_res = K.res != nullptr;
-    auto tile_epilogue = [&](int cotile, int n, int oy0, int ox0, int par) __attribute__((always_inline)) {
+    const bool has_res = K.res != nullptr;
+    auto tile_epilogue = [&]() __attribute__((always_inline)) {
         const bool odd = tx & 1;
-        const int ox = ox0 + 2 * (tx & ~1);
+        const int ox = C.ox0 + 2 * (tx & ~1);
         const bool in_x = ox < K.Wfull;
-        const int co0 = cotile * WN_CO + cg * 16 + 4 * lq;
+        const int co0 = C.cotile * WN_CO + cg * 16 + 4 * lq;
         float bv[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) bv[r] = has_bias ? sbias[par * WN_CO + cg * 16 + 4 * lq + r] : 0.f;
+        for (int r = 0; r < 4; ++r) bv[r] = C.bias(cg * 16 + 4 * lq + r);
         dcvic_static_for<0, 2>([&](auto blk_) {
             constexpr int blk = decltype(blk_)::value;
-            const int oy = oy0 + 2 * (2 * th + blk) + (odd ? 1 : 0);
+            const int oy = C.oy0 + 2 * (2 * th + blk) + (odd ? 1 : 0);
             const bool live = in_x && oy < K.Hfull;
             const long long pix = (long long)oy * K.Wfull + ox;
-            float* const ob = K.out + (long long)n * K.out_bs + pix;
-            const float* const rb = has_res ? K.res + (long long)n * K.res_bs + pix : nullptr;
+            float* const ob = K.out + (long long)C.n * K.out_bs + pix;
+            const float* const rb = has_res ? K.res + (long long)C.n * K.res_bs + pix : nullptr;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 f32x4 rv = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -711,13 +465,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_ups_kernel(const C
                 }
                 float y00 = s0[0] + s0[1], y01 = s0[1] - s0[2];
                 float y10 = s1[0] + s1[1], y11 = s1[1] - s1[2];
-                y00 = dcvic_act(y00 + bv[r], act); y01 = dcvic_act(y01 + bv[r], act);
-                y10 = dcvic_act(y10 + bv[r], act); y11 = dcvic_act(y11 + bv[r], act);
-                const float g0 = odd ? y00 : y10, g1 = odd ? y01 : y11;
-                const float n0 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, g0), 0xB1, 0xF, 0xF, true));
-                const float n1 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, g1), 0xB1, 0xF, 0xF, true));
-                const f32x4 o = odd ? f32x4{n0, n1, y10, y11} : f32x4{y00, y01, n0, n1};
-                if (live && co0 + r < K.Cout) *reinterpret_cast<f32x4*>(ob + (long long)(co0 + r) * HWo) = o + rv;
+                wino22_store(y00, y01, y10, y11, bv[r], act, odd, rv, ob + (long long)(co0 + r) * HWo, live && co0 + r < K.Cout);
             }
         });
 #pragma unroll
@@ -727,27 +475,20 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_ups_kernel(const C
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
     };
-    auto stage_bias = [&](int b, int par) __attribute__((always_inline)) {
-        if (tid < WN_CO) sbias[par * WN_CO + tid] = has_bias ? K.bias[min((b % K.n_cotiles) * WN_CO + tid, K.Cout - 1)] : 0.f;
-    };
-    int c_b = first, c_chunk = 0, c_par = 0;
-    int c_cotile, c_n, c_oy0, c_ox0;
-    decode(first, c_cotile, c_n, c_oy0, c_ox0);
-    stage_bias(first, 0);
-    dma_x(0); x_advance();
+    dma_x(0); X.advance();
     dcvic_static_for<0, 3>([&](auto j_) { dma_u(j_, 0); });
-    u_advance();
-    if (total > 1) { dma_x(1); x_advance(); }
+    U.advance();
+    if (total > 1) { dma_x(1); X.advance(); }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    WN_FENCE();
+    WINO_FENCE();
     dcvic_static_for<0, 3>([&](auto r_) { t_load(r_, t_src); });
-    WN_WAIT_LDS();
+    WINO_WAIT_LDS();
     t_cols(); t_rows();
     dcvic_static_for<0, 5>([&](auto p_) { t_store(p_, t_dst); });
-    WN_WAIT_LDS();
+    WINO_WAIT_LDS();
     __syncthreads();
-    WN_FENCE();
+    WINO_FENCE();
     op_load(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, op_u, op_v);
     auto run_stage = [&](auto more1_, auto more2_, auto par_, int g) __attribute__((always_inline)) {
         constexpr bool more1 = decltype(more1_)::value, more2 = decltype(more2_)::value;
@@ -758,20 +499,20 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_ups_kernel(const C
         dcvic_static_for<0, 5>([&](auto j_) {
             constexpr int j = decltype(j_)::value;
             if constexpr (j < 4) {
-                WN_WAIT_LDS();
+                WINO_WAIT_LDS();
                 op_load(std::integral_constant<int, j + 1>{}, std::integral_constant<int, (j + 1 + PAR) & 1>{}, ua, va);
             } else {
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 __syncthreads();
-                WN_FENCE();
+                WINO_FENCE();
                 if constexpr (more1) op_load(std::integral_constant<int, 0>{}, std::integral_constant<int, PAR ^ 1>{}, op_u + (unsigned)(nxt * WN_US * 4), op_v + (unsigned)(nxt * WN_VS * 4));
             }
-            WN_FENCE();
+            WINO_FENCE();
             dcvic_static_for<0, 8>([&](auto i_) {
                 constexpr int i = decltype(i_)::value, pq = i >> 2, ks = (i >> 1) & 1, blk = i & 1, pp = 2 * j + pq;
                 if constexpr (pp < WU_NPOS) {
                     acc[pp][blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(opA[(j + PAR) & 1][pq * 2 + ks], opB[(j + PAR) & 1][pq][blk * 2 + ks], acc[pp][blk], 0, 0, 0);
-                    WN_FENCE();
+                    WINO_FENCE();
                 }
                 if constexpr (more1 && j == 0 && i == 1) dma_u(std::integral_constant<int, 0>{}, nxt);
                 if constexpr (more1 && j == 0 && i == 5) dma_u(std::integral_constant<int, 1>{}, nxt);
@@ -782,20 +523,16 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_ups_kernel(const C
                 if constexpr (more1 && j == 2 && i == 3) t_rows();
                 if constexpr (more1 && j == 3 && (i & 1)) t_store(std::integral_constant<int, (i >> 1)>{}, vaddr);
                 if constexpr (more1 && j == 3 && i == 6) t_store(std::integral_constant<int, 4>{}, vaddr);
-                WN_FENCE();
+                WINO_FENCE();
             });
         });
-        if constexpr (more2) x_advance();
-        if constexpr (more1) u_advance();
-        if (++c_chunk == S) {
-            tile_epilogue(c_cotile, c_n, c_oy0, c_ox0, c_par);
-            c_chunk = 0; c_b += J; c_par ^= 1;
-            if (c_b < xe) {
-                decode(c_b, c_cotile, c_n, c_oy0, c_ox0);
-                stage_bias(c_b, c_par);
-            }
+        if constexpr (more2) X.advance();
+        if constexpr (more1) U.advance();
+        if (C.stage_done()) {
+            tile_epilogue();
+            C.next_tile();
         }
-        WN_FENCE();
+        WINO_FENCE();
     };
     {
         using P0 = std::integral_constant<int, 0>;
@@ -805,76 +542,30 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_ups_kernel(const C
         if (g + 1 < total) { if (g & 1) run_stage(std::true_type{}, std::false_type{}, P1{}, g); else run_stage(std::true_type{}, std::false_type{}, P0{}, g); ++g; }
         if (g & 1) run_stage(std::false_type{}, std::false_type{}, P1{}, g); else run_stage(std::false_type{}, std::false_type{}, P0{}, g);
     }
-#undef WN_FENCE
-#undef WN_WAIT_LDS
 }
 
-extern "C" size_t dcvic_wino_ups_packed_bytes(int Cin, int Cout) {
-    if (Cin <= 0 || Cout <= 0) return 0;
-    return (size_t)((Cout + WN_CO - 1) / WN_CO) * ((Cin + KC - 1) / KC) * WU_US * sizeof(float);
-}
+static const DcvicWinoPack WU_PACK = {WN_CO, KC, WU_US}, WN_PACK = {WN_CO, KC, WN_US};
+
+extern "C" size_t dcvic_wino_ups_packed_bytes(int Cin, int Cout) { return dcvic_wino_packed_bytes(WU_PACK, Cin, Cout); }
 
 extern "C" int dcvic_wino_ups_pack_f32(const float* w, float* packed, int Cin, int Cout, void* stream) {
-    DCVIC_CHECK_ARG(w && packed && Cin > 0 && Cout > 0, "wino_ups_pack: bad argument");
-    const int n_chunks = (Cin + KC - 1) / KC;
-    const long long total = (long long)((Cout + WN_CO - 1) / WN_CO) * n_chunks * WU_US;
-    wino_ups_pack_kernel<<<dcvic_cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(w, packed, Cin, Cout, n_chunks, total);
-    DCVIC_CHECK_LAUNCH("wino_ups_pack");
-    return DCVIC_OK;
+    return dcvic_wino_pack("wino_ups_pack", wino_ups_pack_kernel, WU_PACK, w, packed, Cin, Cout, stream);
 }
 
 extern "C" int dcvic_conv3x3_wino_ups_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, void* stream) {
-    const DcvicConvRules rules = {"conv3x3_wino_ups", Cin, Cout, DCVIC_MAX_SRC, KC, true, DCVIC_OUT_X2, false, false, 1ll << 28};
     ConvKArgs K;
-    if (const int rc = dcvic_conv_check_io(rules, packed, io, &K)) return rc;
-    DCVIC_CHECK_ARG((io->W & 3) == 0, "conv3x3_wino_ups: input width must be a multiple of 4");
-    if (const int rc = dcvic_conv_tiles("conv3x3_wino_ups", &K, KC, WN_CO, WN_TH, WN_TW)) return rc;
-    static std::atomic<unsigned> attr_mask{0};
-    if (DcvicAttrOnce once_{attr_mask})
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wino_ups_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    conv3x3_wino_ups_kernel<<<dcvic_persistent_grid(K.nblocks), WN_THREADS, WN_LDS_FLOATS * sizeof(float), (hipStream_t)stream>>>(K);
-    DCVIC_CHECK_LAUNCH("conv3x3_wino_ups");
-    return DCVIC_OK;
+    if (const int rc = dcvic_wino_check("conv3x3_wino_ups", DCVIC_OUT_X2, WU_PACK, Cin, Cout, packed, io, &K)) return rc;
+    return dcvic_wino_run<conv3x3_wino_ups_kernel>("conv3x3_wino_ups", &K, WU_PACK, WN_TH, WN_TW, WN_THREADS, WN_LDS_FLOATS * sizeof(float), stream);
 }
 
-extern "C" size_t dcvic_wino_packed_bytes(int Cin, int Cout) {
-    if (Cin <= 0 || Cout <= 0) return 0;
-    return (size_t)((Cout + WN_CO - 1) / WN_CO) * ((Cin + KC - 1) / KC) * WN_US * sizeof(float);
-}
+extern "C" size_t dcvic_wino_packed_bytes(int Cin, int Cout) { return dcvic_wino_packed_bytes(WN_PACK, Cin, Cout); }
 
 extern "C" int dcvic_wino_pack_f32(const float* w, float* packed, int Cin, int Cout, void* stream) {
-    DCVIC_CHECK_ARG(w && packed && Cin > 0 && Cout > 0, "wino_pack: bad argument");
-    const int n_chunks = (Cin + KC - 1) / KC;
-    const long long total = (long long)((Cout + WN_CO - 1) / WN_CO) * n_chunks * WN_US;
-    wino_pack_kernel<<<dcvic_cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(w, packed, Cin, Cout, n_chunks, total);
-    DCVIC_CHECK_LAUNCH("wino_pack");
-    return DCVIC_OK;
+    return dcvic_wino_pack("wino_pack", wino_pack_kernel, WN_PACK, w, packed, Cin, Cout, stream);
 }
 
 extern "C" int dcvic_conv3x3_wino_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, void* stream) {
-    // 16-byte views: the input is staged in 16-byte LDS-DMA segments; plane limit: H x W x 8 < 2^31
-    const DcvicConvRules rules = {"conv3x3_wino", Cin, Cout, DCVIC_MAX_SRC, KC, true, DCVIC_OUT_SAME, false, false, 1ll << 28};
     ConvKArgs K;
-    if (const int rc = dcvic_conv_check_io(rules, packed, io, &K)) return rc;
-    DCVIC_CHECK_ARG((io->W & 3) == 0, "conv3x3_wino: width must be a multiple of 4");
-#ifdef DCVIC_WINO_EXPERIMENTS
-    { const char* e = getenv("DCVIC_WINO_DEBUG"); K.TG = e ? atoi(e) : 0; }   // timing experiments only (wrong results)
-#endif
-    if (const int rc = dcvic_conv_tiles("conv3x3_wino", &K, KC, WN_CO, WN_TH, WN_TW)) return rc;
-    static std::atomic<unsigned> attr_mask{0};
-#ifdef DCVIC_WINO_EXPERIMENTS
-    const int dbg = K.TG >> 4;
-    K.TG &= 15;
-    auto kern = dbg == 1 ? conv3x3_wino_kernel<1> : dbg == 2 ? conv3x3_wino_kernel<2> : dbg == 4 ? conv3x3_wino_kernel<4> : dbg == 8 ? conv3x3_wino_kernel<8> :
-                dbg == 6 ? conv3x3_wino_kernel<6> : dbg == 16 ? conv3x3_wino_kernel<16> : dbg == 32 ? conv3x3_wino_kernel<32> : dbg == 64 ? conv3x3_wino_kernel<64> : dbg == 128 ? conv3x3_wino_kernel<128> : dbg == 256 ? conv3x3_wino_kernel<256> : conv3x3_wino_kernel<0>;
-    if (dbg) hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#else
-    auto kern = conv3x3_wino_kernel<0>;
-#endif
-    if (DcvicAttrOnce once_{attr_mask})
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wino_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    // persistent grid (152 KiB of LDS per workgroup): each workgroup walks its share of the tiles
-    kern<<<dcvic_persistent_grid(K.nblocks), WN_THREADS, WN_LDS_FLOATS * sizeof(float), (hipStream_t)stream>>>(K);
-    DCVIC_CHECK_LAUNCH("conv3x3_wino");
-    return DCVIC_OK;
+    if (const int rc = dcvic_wino_check("conv3x3_wino", DCVIC_OUT_SAME, WN_PACK, Cin, Cout, packed, io, &K)) return rc;
+    return dcvic_wino_run<conv3x3_wino_kernel>("conv3x3_wino", &K, WN_PACK, WN_TH, WN_TW, WN_THREADS, WN_LDS_FLOATS * sizeof(float), stream);
 }

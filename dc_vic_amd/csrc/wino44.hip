@@ -34,7 +34,7 @@
 // LDS: 2 x 24 KiB raw patch + 2 x 36 KiB V + two bias rows = 120.5 KiB.
 // Deterministic and batch-invariant: per position the reduction runs over the 4-channel k-steps ascending inside the MFMA's ordered
 // fmaf chain; the tiling never depends on N.
-#include "conv_common.h"
+#include "wino_stream.h"
 
 // DCVIC_W44_DBG: timing experiments with WRONG results, only in the diagnostic builds of tools/build_w44_experiments.sh (never in
 // libdcvic_hip.so): 1 no stage barrier, 2 no input transform, 4 no LDS-DMA, 8 no operand reads / waits, 16 no tile epilogue,
@@ -42,12 +42,6 @@
 #ifndef DCVIC_W44_DBG
 #define DCVIC_W44_DBG 0
 #endif
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ float dcvic_w44_zero[16];   // zero-initialised: source of padded lanes
 
 #define F4_TH 16
 #define F4_TW 32
@@ -145,84 +139,32 @@ __global__ __launch_bounds__(F4_THREADS, 1) void conv3x3_wino44_kernel(const Con
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // 0..3
 
     const long long HW = (long long)K.H * K.W;
-    const int S = K.n_chunks;                                     // stages (8-channel chunks) per tile
-    const long long x_stride = (long long)F4_KC * HW;
 
-    // ---- PERSISTENT workgroup (as wino.hip): XCD x = blockIdx.x % 8 owns a contiguous range of tile indices
-    int xe;
-    const int J = (int)gridDim.x / NXCD;
-    int first;
-    {
-        const int nb = K.nblocks, q = nb / NXCD, r = nb % NXCD, x = (int)blockIdx.x % NXCD;
-        const int xs = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        xe = xs + (x < r ? q + 1 : q);
-        first = xs + (int)blockIdx.x / NXCD;
-    }
-    if (first >= xe) return;                                      // (uniform: the whole workgroup leaves before any barrier)
-    const int ntile = (xe - first + J - 1) / J;
-    const int total = ntile * S;
-    // tile index b = (cotile, image, tile row, tile column), cotile SLOWEST: an XCD's contiguous range then lies inside one or two
-    // co-tiles, whose weight slabs (36 positions x Cin x 64 co x 4 B = 2.4 MB at Cin = 256) stay in that XCD's 4 MiB L2 for the whole
+    // ---- the workgroup's stage stream (wino_stream.h).  Tile index co-tile SLOWEST: an XCD's contiguous range then lies inside one or
+    // two co-tiles, whose weight slabs (36 positions x Cin x 64 co x 4 B = 2.4 MB at Cin = 256) stay in that XCD's 4 MiB L2 for the whole
     // launch, where every wave's direct weight loads find them.
-    const int n_ptiles = K.nblocks / K.n_cotiles;
-    auto decode = [&](int b, int& cotile, int& n, int& oy0, int& ox0) __attribute__((always_inline)) {
-        cotile = b / n_ptiles; b -= cotile * n_ptiles;
-        const int tile_x = b % K.tiles_x; b /= K.tiles_x;
-        const int tile_y = b % K.tiles_y; b /= K.tiles_y;
-        n = b; oy0 = tile_y * F4_TH; ox0 = tile_x * F4_TW;
-    };
-    auto cotile_of = [&](int b) __attribute__((always_inline)) { return b / n_ptiles; };
-
+    using Tiles = WinoTiles<false, F4_TH, F4_TW>;
+    const Tiles T(K, tid);
+    if (T.empty()) return;
+    const int S = T.S, ntile = T.ntile(), total = T.total;
     // ---- raw-patch DMA: float4 segment e = tid + s*256 of [8 ch][18 rows][10 segments]
-    const float* xp[F4_XSLOTS];
-    int poff[F4_XSLOTS];
-    int x_left = 0, x_n = 0, x_b = first, x_next = 0;
-    auto x_rebase = [&](int c) __attribute__((always_inline)) {
-        int si = 0;
-        if (c >= K.srcC[0]) { c -= K.srcC[0]; si = 1; if (c >= K.srcC[1]) { c -= K.srcC[1]; si = 2; } }
-        const float* base = K.src[si] + (long long)x_n * K.src_bs[si] + (long long)c * HW;
-#pragma unroll
-        for (int s = 0; s < F4_XSLOTS; ++s) xp[s] = poff[s] >= 0 ? base + poff[s] : dcvic_w44_zero;
-        x_left = K.srcC[si] - c;
-    };
-    auto x_setup = [&](int b) __attribute__((always_inline)) {
-        int cot, oy0, ox0;
-        decode(b, cot, x_n, oy0, ox0);
-#pragma unroll
-        for (int s = 0; s < F4_XSLOTS; ++s) {
-            const int e = tid + s * F4_THREADS;
-            int o = -1;
-            if (e < F4_SEGS) {
-                const int k = e / 180, r = e - k * 180;
-                const int py = r / 10, seg = r - py * 10;
-                const int iy = oy0 - 1 + py, ix = ox0 - 4 + 4 * seg;   // W % 4 == 0: a segment is entirely inside or outside the row
-                if (iy >= 0 && iy < K.H && ix >= 0 && ix < K.W) o = (int)(k * HW) + iy * K.W + ix;
-            }
-            poff[s] = o;
+    auto X = wino_x_stream<F4_XSLOTS, F4_THREADS, F4_KC>(T, HW, [&](int e, int oy0, int ox0) __attribute__((always_inline)) {
+        int o = -1;
+        if (e < F4_SEGS) {
+            const int k = e / 180, r = e - k * 180;
+            const int py = r / 10, seg = r - py * 10;
+            const int iy = oy0 - 1 + py, ix = ox0 - 4 + 4 * seg;   // W % 4 == 0: a segment is entirely inside or outside the row
+            if (iy >= 0 && iy < K.H && ix >= 0 && ix < K.W) o = (int)(k * HW) + iy * K.W + ix;
         }
-        x_rebase(0);
-    };
-    x_setup(first);
-    // ---- weights: this wave's slice of the packed image, fetched straight into operand registers.  wp_nxt = the slab of the NEXT
+        return o;
+    });
+    // ---- weights: this wave's slice of the packed image, fetched straight into operand registers.  U.p = the slab of the NEXT
     // stage of the stream (its first k-step is loaded during the second k-step of the current stage).
     const int cg = wave;
     const unsigned u_voff = 16u * (unsigned)(cg * 64 + lane);     // byte offset inside a (k-step, group) block of 4 KiB
-    const float* wp_cur;
-    const float* wp_nxt;
-    int u_b = first, u_next = 0;
-    auto u_setup = [&](int b) __attribute__((always_inline)) { wp_nxt = K.wp + (long long)cotile_of(b) * S * (long long)F4_US; };
-    u_setup(first);
-    wp_cur = wp_nxt;
-    auto u_advance = [&]() __attribute__((always_inline)) {       // wp_nxt: on to the next stage of the stream
-        if (++u_next == S) {
-            u_next = 0;
-            u_b += J;
-            if (u_b < xe) u_setup(u_b);
-        } else {
-            wp_nxt += F4_US;
-        }
-    };
-    u_advance();
+    WinoUStream<F4_US, Tiles> U(T);
+    const float* wp_cur = U.p;
+    U.advance();
 
     // ---- input transform: thread -> channel k = tid / 32 (k-step k / 4), tile t = tid % 32 (block t / 16, column n = t % 16 of the
     //      MFMA's B operand); tile (row ty = t / 8, column tx = t % 8) of the 4 x 8 tile grid
@@ -241,10 +183,8 @@ __global__ __launch_bounds__(F4_THREADS, 1) void conv3x3_wino44_kernel(const Con
     f32x4 acc[32][2];                                             // [position slot][16-tile block]
     f32x4 accv[4][2];
 
-    // All LDS traffic of the loop is inline asm with hand-placed waits (see wino.hip: hipcc guards every LDS access it can see with
+    // All LDS traffic of the loop is inline asm with hand-placed waits (see wino_stream.h: hipcc guards every LDS access it can see with
     // `s_waitcnt vmcnt(0)` while an LDS-DMA is in flight); so are the weight loads (their landing is awaited once per k-step).
-#define F4_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define F4_WAIT_LDS() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); F4_FENCE(); } while (0)
     // the 6x6 patch of this thread, row r = (dl[r] | dm[r][0..3] | dr[r]); transformed in place; after the row pass the edge
     // columns live in de[r] = (column 0, column 5)
     float dl[6], dr[6];
@@ -298,31 +238,17 @@ __global__ __launch_bounds__(F4_THREADS, 1) void conv3x3_wino44_kernel(const Con
     };
     auto dma_x = [&](auto s_, int buf) {
         constexpr int sl = decltype(s_)::value;
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const float4*>(xp[sl]), (lds_ptr_t)(smem + buf * F4_XS + (wave * 64 + sl * F4_THREADS) * 4), 16, 0, 0);
-    };
-    auto x_advance = [&]() __attribute__((always_inline)) {
-        if (++x_next == S) {
-            x_next = 0;
-            x_b += J;
-            if (x_b < xe) x_setup(x_b);
-        } else {
-            x_left -= F4_KC;
-            if (x_left > 0) {
-#pragma unroll
-                for (int sl = 0; sl < F4_XSLOTS; ++sl) xp[sl] += poff[sl] >= 0 ? x_stride : 0ll;   // (padding lanes stay on the zero word)
-            } else {
-                x_rebase(x_next * F4_KC);
-            }
-        }
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const float4*>(X.xp[sl]), (lds_ptr_t)(smem + buf * F4_XS + (wave * 64 + sl * F4_THREADS) * 4), 16, 0, 0);
     };
 
     // ---- epilogue of one tile, in registers: lane holds element (co = 16 cg + 4 (lane / 16) + r, tile = 16 blk + lane % 16) of all 36
     // positions.  A^T M A per (block, r): 6 column passes + 4 row passes, bias -> act -> (+ res) -> four 16-byte row stores.
-    float* const sbias = smem + F4_OFF_BIAS;                      // [2][64], by tile parity
+    WinoTileCursor<F4_CO, Tiles> C(T, smem + F4_OFF_BIAS);        // compute stream: the tile, its bias row in [2][64] by tile parity
     const int e_n = lane & 15, lq = lane >> 4;
     const float neg_slope = K.act == DCVIC_ACT_RELU ? 0.f : K.act == DCVIC_ACT_LRELU02 ? 0.2f : 1.f;
-    const bool has_bias = K.bias != nullptr, has_res = K.res != nullptr;
-    auto tile_epilogue = [&](int cotile, int n, int oy0, int ox0, int par) __attribute__((always_inline)) {
+    const bool has_res = K.res != nullptr;
+    auto tile_epilogue = [&]() __attribute__((always_inline)) {
+        const int cotile = C.cotile, n = C.n, oy0 = C.oy0, ox0 = C.ox0;
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");          // the inline-asm MFMAs' results are read below
         auto A = [&](auto idx_, auto blk_, int r) __attribute__((always_inline)) -> float {
             constexpr int idx = decltype(idx_)::value, blk = decltype(blk_)::value;
@@ -336,7 +262,7 @@ __global__ __launch_bounds__(F4_THREADS, 1) void conv3x3_wino44_kernel(const Con
         const int co0 = cotile * F4_CO + cg * 16 + 4 * lq;
         float bv[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) bv[r] = has_bias ? sbias[par * F4_CO + cg * 16 + 4 * lq + r] : 0.f;
+        for (int r = 0; r < 4; ++r) bv[r] = C.bias(cg * 16 + 4 * lq + r);
         float gs[4] = {0.f, 0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};   // GroupNorm partials of this lane's four channels
         dcvic_static_for<0, 2>([&](auto blk_) {
             constexpr int blk = decltype(blk_)::value;
@@ -419,34 +345,27 @@ __global__ __launch_bounds__(F4_THREADS, 1) void conv3x3_wino44_kernel(const Con
             }
         }
     };
-    auto stage_bias = [&](int b, int par) __attribute__((always_inline)) {
-        if (tid < F4_CO) sbias[par * F4_CO + tid] = has_bias ? K.bias[min(cotile_of(b) * F4_CO + tid, K.Cout - 1)] : 0.f;
-    };
 
     // ---- pipeline
-    int c_b = first, c_par = 0;                                   // compute stream: tile, tile parity
-    int c_cotile, c_n, c_oy0, c_ox0;
-    decode(first, c_cotile, c_n, c_oy0, c_ox0);
-    stage_bias(first, 0);
     // prologue: X(0) -> Xr[0], X(1) -> Xr[1], U(stage 0, k-step 0) -> uA[0]; every thread transforms its patch of stage 0 -> V[0]
     dcvic_static_for<0, F4_XSLOTS>([&](auto s_) { dma_x(s_, 0); });
-    x_advance();
+    X.advance();
     if (total > 1) {
         dcvic_static_for<0, F4_XSLOTS>([&](auto s_) { dma_x(s_, 1); });
-        x_advance();
+        X.advance();
     }
     dcvic_static_for<0, 9>([&](auto pg_) { u_load(std::integral_constant<int, 0>{}, pg_, wp_cur); });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    F4_FENCE();
+    WINO_FENCE();
     dcvic_static_for<0, 6>([&](auto r_) { t_load(r_, t_src); });
-    F4_WAIT_LDS();
+    WINO_WAIT_LDS();
     dcvic_static_for<0, 6>([&](auto c_) { dcvic_static_for<0, 4>([&](auto q_) { t_col(c_, q_); }); });
     dcvic_static_for<0, 6>([&](auto a_) { dcvic_static_for<0, 4>([&](auto q_) { t_row(a_, q_); }); });
     dcvic_static_for<0, 12>([&](auto i_) { t_store(i_, t_dst); });
-    F4_WAIT_LDS();
+    WINO_WAIT_LDS();
     __syncthreads();
-    F4_FENCE();
+    WINO_FENCE();
     op_load(std::integral_constant<int, 0>{}, op_v);
 
     // One stage = 18 operand groups G = 9 ks + pg (k-step, position group) x 8 MFMAs (4 positions x 2 blocks) = 144 slots.  The body has
@@ -468,17 +387,17 @@ __global__ __launch_bounds__(F4_THREADS, 1) void conv3x3_wino44_kernel(const Con
                 if constexpr (!(DCVIC_W44_DBG & 8)) {
                     if constexpr (G == 9) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                     else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    F4_FENCE();
+                    WINO_FENCE();
                     op_load(std::integral_constant<int, G + 1>{}, va);
                 }
             } else {
                 if constexpr (DCVIC_W44_DBG & 64) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 if constexpr (!(DCVIC_W44_DBG & 1)) __syncthreads();
-                F4_FENCE();
+                WINO_FENCE();
                 if constexpr (!(DCVIC_W44_DBG & 8)) op_load(std::integral_constant<int, 0>{}, op_v + (unsigned)(nxt * F4_VS * 4));
             }
-            F4_FENCE();
+            WINO_FENCE();
             dcvic_static_for<0, 8>([&](auto q_) {
                 constexpr int q = decltype(q_)::value, ps = q >> 1, blk = q & 1;
                 if constexpr (!(DCVIC_W44_DBG & 32)) {
@@ -486,7 +405,7 @@ __global__ __launch_bounds__(F4_THREADS, 1) void conv3x3_wino44_kernel(const Con
                     if constexpr (pg < 8) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc[pg * 4 + ps][blk]) : "v"(a_), "v"(b_));
                     else asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(accv[ps][blk]) : "v"(a_), "v"(b_));
                 }
-                F4_FENCE();
+                WINO_FENCE();
                 constexpr int sl = 8 * G + q;                     // 0 .. 143
                 constexpr int h = sl % 72;                        // slot inside the k-step
                 // memory: per k-step three DMA pieces of X(s + 2) (slots 1, 5, 9), then the nine weight loads of the NEXT k-step
@@ -494,7 +413,7 @@ __global__ __launch_bounds__(F4_THREADS, 1) void conv3x3_wino44_kernel(const Con
                 if constexpr (!(DCVIC_W44_DBG & 4) && (h & 3) == 1 && h < 12) dma_x(std::integral_constant<int, 3 * ks + h / 4>{}, cur);
                 if constexpr (!(DCVIC_W44_DBG & 4) && (h & 3) == 1 && h >= 12 && h < 48) {
                     if constexpr (ks == 0) u_load(std::integral_constant<int, 1>{}, std::integral_constant<int, (h / 4 - 3)>{}, wp_cur);
-                    else u_load(std::integral_constant<int, 0>{}, std::integral_constant<int, (h / 4 - 3)>{}, wp_nxt);
+                    else u_load(std::integral_constant<int, 0>{}, std::integral_constant<int, (h / 4 - 3)>{}, U.p);
                 }
                 if constexpr (!(DCVIC_W44_DBG & 2)) {
                     // transform of X(s + 1): six row loads at slots 2, 3, 6, 7, 10, 11 (landed by the wait in front of group 2), column pass
@@ -506,10 +425,10 @@ __global__ __launch_bounds__(F4_THREADS, 1) void conv3x3_wino44_kernel(const Con
                         t_row(std::integral_constant<int, (((sl - 72) / 2) / 4)>{}, std::integral_constant<int, (((sl - 72) / 2) % 4)>{});
                     if constexpr (sl >= 120 && sl < 132) t_store(std::integral_constant<int, sl - 120>{}, vaddr);
                 }
-                F4_FENCE();
+                WINO_FENCE();
             });
         });
-        F4_FENCE();
+        WINO_FENCE();
     };
     {
         int s = 0;
@@ -526,39 +445,34 @@ __global__ __launch_bounds__(F4_THREADS, 1) void conv3x3_wino44_kernel(const Con
                 for (int j = 0; j < 2; ++j) accv[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
             for (int c = 0; c < S; ++c, ++s) {
                 run_stage(s);
-                if (s + 2 < total) x_advance();                   // the DMA of this stage fetched X(s + 2): on to X(s + 3)
-                wp_cur = wp_nxt;
-                if (s + 2 < total) u_advance();                   // wp_nxt: slab of stage s + 2
+                if (s + 2 < total) X.advance();                   // the DMA of this stage fetched X(s + 2): on to X(s + 3)
+                wp_cur = U.p;
+                if (s + 2 < total) U.advance();                   // U.p: slab of stage s + 2
             }
-            if constexpr (!(DCVIC_W44_DBG & 16)) tile_epilogue(c_cotile, c_n, c_oy0, c_ox0, c_par);
-            c_b += J; c_par ^= 1;
-            if (c_b < xe) {
-                decode(c_b, c_cotile, c_n, c_oy0, c_ox0);
-                stage_bias(c_b, c_par);
-            }
+            if constexpr (!(DCVIC_W44_DBG & 16)) tile_epilogue();
+            C.next_tile();
         }
     }
-#undef F4_FENCE
-#undef F4_WAIT_LDS
 }
 
-extern "C" size_t dcvic_wino44_packed_bytes(int Cin, int Cout) {
-    if (Cin <= 0 || Cout <= 0) return 0;
-    return (size_t)((Cout + F4_CO - 1) / F4_CO) * ((Cin + F4_KC - 1) / F4_KC) * F4_US * sizeof(float);
-}
+static const DcvicWinoPack F4_PACK = {F4_CO, F4_KC, F4_US};
+
+extern "C" size_t dcvic_wino44_packed_bytes(int Cin, int Cout) { return dcvic_wino_packed_bytes(F4_PACK, Cin, Cout); }
 
 extern "C" int dcvic_wino44_pack_f32(const float* w, float* packed, int Cin, int Cout, void* stream) {
-    DCVIC_CHECK_ARG(w && packed && Cin > 0 && Cout > 0, "wino44_pack: bad argument");
-    const int n_chunks = (Cin + F4_KC - 1) / F4_KC;
-    const long long total = (long long)((Cout + F4_CO - 1) / F4_CO) * n_chunks * F4_US;
-    wino44_pack_kernel<<<dcvic_cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(w, packed, Cin, Cout, n_chunks, total);
-    DCVIC_CHECK_LAUNCH("wino44_pack");
-    return DCVIC_OK;
+    return dcvic_wino_pack("wino44_pack", wino44_pack_kernel, F4_PACK, w, packed, Cin, Cout, stream);
 }
 
 extern "C" int dcvic_wino44_stats_tiles(int H, int W) { return H > 0 && W > 0 ? ((H + F4_TH - 1) / F4_TH) * ((W + F4_TW - 1) / F4_TW) : 0; }
 
-static int wino44_launch(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream);
+static int wino44_launch(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream) {
+    ConvKArgs K;
+    if (const int rc = dcvic_wino_check("conv3x3_wino44", DCVIC_OUT_SAME, F4_PACK, Cin, Cout, packed, io, &K)) return rc;
+    DCVIC_CHECK_ARG(io->act == DCVIC_ACT_NONE || io->act == DCVIC_ACT_RELU || io->act == DCVIC_ACT_LRELU02,
+                    "conv3x3_wino44: activation %d not supported (none / ReLU / LeakyReLU(0.2) only)", io->act);
+    K.gn_part = gn_part;
+    return dcvic_wino_run<conv3x3_wino44_kernel>("conv3x3_wino44", &K, F4_PACK, F4_TH, F4_TW, F4_THREADS, F4_LDS_FLOATS * sizeof(float), stream);
+}
 
 extern "C" int dcvic_conv3x3_wino44_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, void* stream) {
     return wino44_launch(Cin, Cout, packed, io, nullptr, stream);
@@ -567,23 +481,4 @@ extern "C" int dcvic_conv3x3_wino44_f32(int Cin, int Cout, const float* packed, 
 extern "C" int dcvic_conv3x3_wino44_stats_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream) {
     DCVIC_CHECK_ARG(gn_part, "conv3x3_wino44_stats: null statistics buffer");
     return wino44_launch(Cin, Cout, packed, io, gn_part, stream);
-}
-
-static int wino44_launch(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream) {
-    // 16-byte views: the input is staged in 16-byte LDS-DMA segments; plane limit: H x W x 8 < 2^31
-    const DcvicConvRules rules = {"conv3x3_wino44", Cin, Cout, DCVIC_MAX_SRC, F4_KC, true, DCVIC_OUT_SAME, false, false, 1ll << 28};
-    ConvKArgs K;
-    if (const int rc = dcvic_conv_check_io(rules, packed, io, &K)) return rc;
-    DCVIC_CHECK_ARG((io->W & 3) == 0, "conv3x3_wino44: width must be a multiple of 4");
-    DCVIC_CHECK_ARG(io->act == DCVIC_ACT_NONE || io->act == DCVIC_ACT_RELU || io->act == DCVIC_ACT_LRELU02,
-                    "conv3x3_wino44: activation %d not supported (none / ReLU / LeakyReLU(0.2) only)", io->act);
-    K.gn_part = gn_part;
-    if (const int rc = dcvic_conv_tiles("conv3x3_wino44", &K, F4_KC, F4_CO, F4_TH, F4_TW)) return rc;
-    static std::atomic<unsigned> attr_mask{0};
-    if (DcvicAttrOnce once_{attr_mask})
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wino44_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    // persistent grid: each workgroup walks its share of the tiles
-    conv3x3_wino44_kernel<<<dcvic_persistent_grid(K.nblocks), F4_THREADS, F4_LDS_FLOATS * sizeof(float), (hipStream_t)stream>>>(K);
-    DCVIC_CHECK_LAUNCH("conv3x3_wino44");
-    return DCVIC_OK;
 }

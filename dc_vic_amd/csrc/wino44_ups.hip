@@ -33,13 +33,7 @@
 // LDS: 2 x 8 KiB raw patch + 2 x 25 KiB V + two bias rows = 66.5 KiB.
 // Deterministic and batch-invariant: per position the reduction runs over the 4-channel k-steps ascending inside the MFMA's ordered fmaf
 // chain; the tiling never depends on N.
-#include "conv_common.h"
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ float dcvic_w44u_zero[16];   // zero-initialised: source of padded lanes
+#include "wino_stream.h"
 
 #define U4_TH 16           // output tile rows / columns
 #define U4_TW 32
@@ -129,82 +123,30 @@ __global__ __launch_bounds__(U4_THREADS, 1) void conv3x3_wino44_ups_kernel(const
 
     const long long HW = (long long)K.H * K.W;                    // low-resolution input plane
     const long long HWo = (long long)K.Hfull * K.Wfull;           // output plane
-    const int S = K.n_chunks;
-    const long long x_stride = (long long)U4_KC * HW;
 
-    // ---- PERSISTENT workgroup (as wino44.hip): XCD x = blockIdx.x % 8 owns a contiguous range of tile indices
-    int xe;
-    const int J = (int)gridDim.x / NXCD;
-    int first;
-    {
-        const int nb = K.nblocks, q = nb / NXCD, r = nb % NXCD, x = (int)blockIdx.x % NXCD;
-        const int xs = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        xe = xs + (x < r ? q + 1 : q);
-        first = xs + (int)blockIdx.x / NXCD;
-    }
-    if (first >= xe) return;                                      // (uniform: the whole workgroup leaves before any barrier)
-    const int ntile = (xe - first + J - 1) / J;
-    const int total = ntile * S;
-    // tile index b = (cotile, image, tile row, tile column), cotile slowest (an XCD's L2 keeps its weight slab)
-    const int n_ptiles = K.nblocks / K.n_cotiles;
-    auto decode = [&](int b, int& cotile, int& n, int& oy0, int& ox0) __attribute__((always_inline)) {
-        cotile = b / n_ptiles; b -= cotile * n_ptiles;
-        const int tile_x = b % K.tiles_x; b /= K.tiles_x;
-        const int tile_y = b % K.tiles_y; b /= K.tiles_y;
-        n = b; oy0 = tile_y * U4_TH; ox0 = tile_x * U4_TW;        // OUTPUT coordinates
-    };
-    auto cotile_of = [&](int b) __attribute__((always_inline)) { return b / n_ptiles; };
-
+    // ---- the workgroup's stage stream (wino_stream.h), tile index co-tile slowest (an XCD's L2 keeps its weight slab), tiles of the OUTPUT
+    using Tiles = WinoTiles<false, U4_TH, U4_TW>;
+    const Tiles T(K, tid);
+    if (T.empty()) return;
+    const int S = T.S, ntile = T.ntile(), total = T.total;
     // ---- raw-patch DMA: float4 segment e = tid + s*256 of [8 ch][10 low-resolution rows][6 segments]
-    const float* xp[U4_XSLOTS];
-    int poff[U4_XSLOTS];
-    int x_left = 0, x_n = 0, x_b = first, x_next = 0;
-    auto x_rebase = [&](int c) __attribute__((always_inline)) {
-        int si = 0;
-        if (c >= K.srcC[0]) { c -= K.srcC[0]; si = 1; if (c >= K.srcC[1]) { c -= K.srcC[1]; si = 2; } }
-        const float* base = K.src[si] + (long long)x_n * K.src_bs[si] + (long long)c * HW;
-#pragma unroll
-        for (int s = 0; s < U4_XSLOTS; ++s) xp[s] = poff[s] >= 0 ? base + poff[s] : dcvic_w44u_zero;
-        x_left = K.srcC[si] - c;
-    };
-    auto x_setup = [&](int b) __attribute__((always_inline)) {
-        int cot, oy0, ox0;
-        decode(b, cot, x_n, oy0, ox0);
-#pragma unroll
-        for (int s = 0; s < U4_XSLOTS; ++s) {
-            const int e = tid + s * U4_THREADS;
-            int o = -1;
-            if (e < U4_SEGS) {
-                const int k = e / 60, r = e - k * 60;
-                const int py = r / 6, seg = r - py * 6;
-                const int iy = oy0 / 2 - 1 + py, ix = ox0 / 2 - 4 + 4 * seg;   // W % 4 == 0: a segment is entirely inside or outside the row
-                if (iy >= 0 && iy < K.H && ix >= 0 && ix < K.W) o = (int)(k * HW) + iy * K.W + ix;
-            }
-            poff[s] = o;
+    auto X = wino_x_stream<U4_XSLOTS, U4_THREADS, U4_KC>(T, HW, [&](int e, int oy0, int ox0) __attribute__((always_inline)) {
+        int o = -1;
+        if (e < U4_SEGS) {
+            const int k = e / 60, r = e - k * 60;
+            const int py = r / 6, seg = r - py * 6;
+            const int iy = oy0 / 2 - 1 + py, ix = ox0 / 2 - 4 + 4 * seg;   // W % 4 == 0: a segment is entirely inside or outside the row
+            if (iy >= 0 && iy < K.H && ix >= 0 && ix < K.W) o = (int)(k * HW) + iy * K.W + ix;
         }
-        x_rebase(0);
-    };
-    x_setup(first);
-    // ---- weights: this wave's slice of the packed image, straight into operand registers (wp_nxt: slab of the NEXT stage)
+        return o;
+    });
+    // ---- weights: this wave's slice of the packed image, straight into operand registers (U.p: slab of the NEXT stage)
     const int cg = wave;
     const unsigned u_voff = 16u * (unsigned)(cg * 64 + lane);     // groups 0..5: byte offset inside a 4 KiB (k-step, group) block
     const unsigned u_soff = 4u * (unsigned)(cg * 64 + lane);      // position 24
-    const float* wp_cur;
-    const float* wp_nxt;
-    int u_b = first, u_next = 0;
-    auto u_setup = [&](int b) __attribute__((always_inline)) { wp_nxt = K.wp + (long long)cotile_of(b) * S * (long long)U4_US; };
-    u_setup(first);
-    wp_cur = wp_nxt;
-    auto u_advance = [&]() __attribute__((always_inline)) {
-        if (++u_next == S) {
-            u_next = 0;
-            u_b += J;
-            if (u_b < xe) u_setup(u_b);
-        } else {
-            wp_nxt += U4_US;
-        }
-    };
-    u_advance();
+    WinoUStream<U4_US, Tiles> U(T);
+    const float* wp_cur = U.p;
+    U.advance();
 
     // ---- input transform: thread -> channel k = tid / 32 (k-step k / 4), tile t = tid % 32 (block t / 16, column n = t % 16 of the
     //      MFMA's B operand); tile (row ty = t / 8, column tx = t % 8) of the 4 x 8 tile grid = low-resolution rows 2 ty - 1 .. 2 ty + 2,
@@ -221,8 +163,6 @@ __global__ __launch_bounds__(U4_THREADS, 1) void conv3x3_wino44_ups_kernel(const
     // epilogue reads them with explicit v_accvgpr_read (as in wino44.hip: the builtin lets hipcc move them through VGPRs / scratch)
     f32x4 acc[25][2];                                             // [position][16-tile block]
 
-#define U4_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define U4_WAIT_LDS() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); U4_FENCE(); } while (0)
     // the 4x4 patch of this thread: row r = (pl[r] | pm[r].x, pm[r].y | pr[r]); column pass -> cq[5][4], row pass -> vv[5][5]
     float pl[4], pr[4];
     f32x2 pm[4];
@@ -291,31 +231,17 @@ __global__ __launch_bounds__(U4_THREADS, 1) void conv3x3_wino44_ups_kernel(const
     };
     auto dma_x = [&](auto s_, int buf) {
         constexpr int sl = decltype(s_)::value;
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const float4*>(xp[sl]), (lds_ptr_t)(smem + buf * U4_XS + (wave * 64 + sl * U4_THREADS) * 4), 16, 0, 0);
-    };
-    auto x_advance = [&]() __attribute__((always_inline)) {
-        if (++x_next == S) {
-            x_next = 0;
-            x_b += J;
-            if (x_b < xe) x_setup(x_b);
-        } else {
-            x_left -= U4_KC;
-            if (x_left > 0) {
-#pragma unroll
-                for (int sl = 0; sl < U4_XSLOTS; ++sl) xp[sl] += poff[sl] >= 0 ? x_stride : 0ll;   // (padding lanes stay on the zero word)
-            } else {
-                x_rebase(x_next * U4_KC);
-            }
-        }
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const float4*>(X.xp[sl]), (lds_ptr_t)(smem + buf * U4_XS + (wave * 64 + sl * U4_THREADS) * 4), 16, 0, 0);
     };
 
     // ---- epilogue of one tile, in registers: lane holds element (co = 16 cg + 4 (lane / 16) + r, tile = 16 blk + lane % 16) of all 25
     // positions.  A^T M A per (block, r): 5 column passes + 4 row passes, bias -> act -> (+ res) -> four 16-byte row stores.
-    float* const sbias = smem + U4_OFF_BIAS;                      // [2][64], by tile parity
+    WinoTileCursor<U4_CO, Tiles> C(T, smem + U4_OFF_BIAS);        // compute stream: the tile, its bias row in [2][64] by tile parity
     const int e_n = lane & 15, lq = lane >> 4;
     const float neg_slope = K.act == DCVIC_ACT_RELU ? 0.f : K.act == DCVIC_ACT_LRELU02 ? 0.2f : 1.f;
-    const bool has_bias = K.bias != nullptr, has_res = K.res != nullptr;
-    auto tile_epilogue = [&](int cotile, int n, int oy0, int ox0, int par) __attribute__((always_inline)) {
+    const bool has_res = K.res != nullptr;
+    auto tile_epilogue = [&]() __attribute__((always_inline)) {
+        const int cotile = C.cotile, n = C.n, oy0 = C.oy0, ox0 = C.ox0;
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");          // the inline-asm MFMAs' results are read below
         auto A = [&](auto idx_, auto blk_, int r) __attribute__((always_inline)) -> float {
             constexpr int idx = decltype(idx_)::value, blk = decltype(blk_)::value;
@@ -327,7 +253,7 @@ __global__ __launch_bounds__(U4_THREADS, 1) void conv3x3_wino44_ups_kernel(const
         const int co0 = cotile * U4_CO + cg * 16 + 4 * lq;
         float bv[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) bv[r] = has_bias ? sbias[par * U4_CO + cg * 16 + 4 * lq + r] : 0.f;
+        for (int r = 0; r < 4; ++r) bv[r] = C.bias(cg * 16 + 4 * lq + r);
         float gs[4] = {0.f, 0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};   // GroupNorm partials of this lane's four channels
         dcvic_static_for<0, 2>([&](auto blk_) {
             const int t = decltype(blk_)::value * 16 + e_n;
@@ -405,34 +331,27 @@ __global__ __launch_bounds__(U4_THREADS, 1) void conv3x3_wino44_ups_kernel(const
             }
         }
     };
-    auto stage_bias = [&](int b, int par) __attribute__((always_inline)) {
-        if (tid < U4_CO) sbias[par * U4_CO + tid] = has_bias ? K.bias[min(cotile_of(b) * U4_CO + tid, K.Cout - 1)] : 0.f;
-    };
 
     // ---- pipeline
-    int c_b = first, c_par = 0;
-    int c_cotile, c_n, c_oy0, c_ox0;
-    decode(first, c_cotile, c_n, c_oy0, c_ox0);
-    stage_bias(first, 0);
     // prologue: X(0) -> Xr[0], X(1) -> Xr[1], U(stage 0, k-step 0) -> uA[0] / uS[0]; every thread transforms its patch of stage 0 -> V[0]
     dcvic_static_for<0, U4_XSLOTS>([&](auto s_) { dma_x(s_, 0); });
-    x_advance();
+    X.advance();
     if (total > 1) {
         dcvic_static_for<0, U4_XSLOTS>([&](auto s_) { dma_x(s_, 1); });
-        x_advance();
+        X.advance();
     }
     dcvic_static_for<0, 7>([&](auto pg_) { u_load(std::integral_constant<int, 0>{}, pg_, wp_cur); });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    U4_FENCE();
+    WINO_FENCE();
     dcvic_static_for<0, 4>([&](auto r_) { t_load(r_, t_src); });
-    U4_WAIT_LDS();
+    WINO_WAIT_LDS();
     dcvic_static_for<0, 4>([&](auto c_) { dcvic_static_for<0, 3>([&](auto q_) { t_col(c_, q_); }); });
     dcvic_static_for<0, 5>([&](auto a_) { dcvic_static_for<0, 3>([&](auto q_) { t_row(a_, q_); }); });
     dcvic_static_for<0, 7>([&](auto i_) { t_store(i_, t_dst, t_dst1); });
-    U4_WAIT_LDS();
+    WINO_WAIT_LDS();
     __syncthreads();
-    U4_FENCE();
+    WINO_FENCE();
     op_load(std::integral_constant<int, 0>{}, op_v, op_s);
 
     // One stage = 14 operand groups G = 7 ks + pg (k-step, group): groups 0..5 of a k-step are 8 MFMAs (4 positions x 2 blocks), group 6
@@ -453,15 +372,15 @@ __global__ __launch_bounds__(U4_THREADS, 1) void conv3x3_wino44_ups_kernel(const
             if constexpr (G < 13) {
                 if constexpr (G == 7) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                U4_FENCE();
+                WINO_FENCE();
                 op_load(std::integral_constant<int, G + 1>{}, va, vs);
             } else {
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 __syncthreads();
-                U4_FENCE();
+                WINO_FENCE();
                 op_load(std::integral_constant<int, 0>{}, op_v + (unsigned)(nxt * U4_VS * 4), op_s + (unsigned)(nxt * U4_VS * 4));
             }
-            U4_FENCE();
+            WINO_FENCE();
             constexpr int NQ = pg < 6 ? 8 : 2;
             dcvic_static_for<0, NQ>([&](auto q_) {
                 constexpr int q = decltype(q_)::value;
@@ -473,7 +392,7 @@ __global__ __launch_bounds__(U4_THREADS, 1) void conv3x3_wino44_ups_kernel(const
                     const float a_ = uS[ks], b_ = opS[ks][q];
                     asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc[24][q]) : "v"(a_), "v"(b_));
                 }
-                U4_FENCE();
+                WINO_FENCE();
                 constexpr int h = (pg < 6 ? 8 * pg : 48) + q;     // slot inside the k-step, 0 .. 49
                 constexpr int sl = 50 * ks + h;                   // 0 .. 99
                 // memory: per k-step one DMA piece of X(s + 2) (slot 1), then the seven weight loads of the NEXT k-step (slots 5 .. 29):
@@ -481,7 +400,7 @@ __global__ __launch_bounds__(U4_THREADS, 1) void conv3x3_wino44_ups_kernel(const
                 if constexpr (h == 1) dma_x(std::integral_constant<int, ks>{}, cur);
                 if constexpr ((h & 3) == 1 && h >= 5 && h < 33) {
                     if constexpr (ks == 0) u_load(std::integral_constant<int, 1>{}, std::integral_constant<int, (h - 5) / 4>{}, wp_cur);
-                    else u_load(std::integral_constant<int, 0>{}, std::integral_constant<int, (h - 5) / 4>{}, wp_nxt);
+                    else u_load(std::integral_constant<int, 0>{}, std::integral_constant<int, (h - 5) / 4>{}, U.p);
                 }
                 // transform of X(s + 1): four row loads at slots 2, 3, 6, 7 (landed by the wait in front of group 1), 27 thirds of the column
                 // (4) and row (5) passes at the even slots 10 .. 62, the seven stores at slots 64 .. 70
@@ -492,10 +411,10 @@ __global__ __launch_bounds__(U4_THREADS, 1) void conv3x3_wino44_ups_kernel(const
                     else t_row(std::integral_constant<int, tr - 4>{}, std::integral_constant<int, third>{});
                 }
                 if constexpr (sl >= 64 && sl < 71) t_store(std::integral_constant<int, sl - 64>{}, vaddr, vaddr1);
-                U4_FENCE();
+                WINO_FENCE();
             });
         });
-        U4_FENCE();
+        WINO_FENCE();
     };
     {
         int s = 0;
@@ -507,37 +426,32 @@ __global__ __launch_bounds__(U4_THREADS, 1) void conv3x3_wino44_ups_kernel(const
                 for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
             for (int c = 0; c < S; ++c, ++s) {
                 run_stage(s);
-                if (s + 2 < total) x_advance();                   // the DMA of this stage fetched X(s + 2): on to X(s + 3)
-                wp_cur = wp_nxt;
-                if (s + 2 < total) u_advance();                   // wp_nxt: slab of stage s + 2
+                if (s + 2 < total) X.advance();                   // the DMA of this stage fetched X(s + 2): on to X(s + 3)
+                wp_cur = U.p;
+                if (s + 2 < total) U.advance();                   // U.p: slab of stage s + 2
             }
-            tile_epilogue(c_cotile, c_n, c_oy0, c_ox0, c_par);
-            c_b += J; c_par ^= 1;
-            if (c_b < xe) {
-                decode(c_b, c_cotile, c_n, c_oy0, c_ox0);
-                stage_bias(c_b, c_par);
-            }
+            tile_epilogue();
+            C.next_tile();
         }
     }
-#undef U4_FENCE
-#undef U4_WAIT_LDS
 }
 
-extern "C" size_t dcvic_wino44_ups_packed_bytes(int Cin, int Cout) {
-    if (Cin <= 0 || Cout <= 0) return 0;
-    return (size_t)((Cout + U4_CO - 1) / U4_CO) * ((Cin + U4_KC - 1) / U4_KC) * U4_US * sizeof(float);
-}
+static const DcvicWinoPack U4_PACK = {U4_CO, U4_KC, U4_US};
+
+extern "C" size_t dcvic_wino44_ups_packed_bytes(int Cin, int Cout) { return dcvic_wino_packed_bytes(U4_PACK, Cin, Cout); }
 
 extern "C" int dcvic_wino44_ups_pack_f32(const float* w, float* packed, int Cin, int Cout, void* stream) {
-    DCVIC_CHECK_ARG(w && packed && Cin > 0 && Cout > 0, "wino44_ups_pack: bad argument");
-    const int n_chunks = (Cin + U4_KC - 1) / U4_KC;
-    const long long total = (long long)((Cout + U4_CO - 1) / U4_CO) * n_chunks * U4_US;
-    wino44_ups_pack_kernel<<<dcvic_cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(w, packed, Cin, Cout, n_chunks, total);
-    DCVIC_CHECK_LAUNCH("wino44_ups_pack");
-    return DCVIC_OK;
+    return dcvic_wino_pack("wino44_ups_pack", wino44_ups_pack_kernel, U4_PACK, w, packed, Cin, Cout, stream);
 }
 
-static int wino44_ups_launch(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream);
+static int wino44_ups_launch(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream) {
+    ConvKArgs K;
+    if (const int rc = dcvic_wino_check("conv3x3_wino44_ups", DCVIC_OUT_X2, U4_PACK, Cin, Cout, packed, io, &K)) return rc;
+    DCVIC_CHECK_ARG(io->act == DCVIC_ACT_NONE || io->act == DCVIC_ACT_RELU || io->act == DCVIC_ACT_LRELU02,
+                    "conv3x3_wino44_ups: activation %d not supported (none / ReLU / LeakyReLU(0.2) only)", io->act);
+    K.gn_part = gn_part;
+    return dcvic_wino_run<conv3x3_wino44_ups_kernel>("conv3x3_wino44_ups", &K, U4_PACK, U4_TH, U4_TW, U4_THREADS, U4_LDS_FLOATS * sizeof(float), stream);
+}
 
 // Replaces dcvic_conv3x3_wino_ups_f32 (ldm Upsample, model.py:42-57) on the layers that allow F(4x4, 3x3)
 extern "C" int dcvic_conv3x3_wino44_ups_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, void* stream) {
@@ -549,22 +463,4 @@ extern "C" int dcvic_conv3x3_wino44_ups_f32(int Cin, int Cout, const float* pack
 extern "C" int dcvic_conv3x3_wino44_ups_stats_f32(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream) {
     DCVIC_CHECK_ARG(gn_part, "conv3x3_wino44_ups_stats: null statistics buffer");
     return wino44_ups_launch(Cin, Cout, packed, io, gn_part, stream);
-}
-
-static int wino44_ups_launch(int Cin, int Cout, const float* packed, const dcvic_conv_io* io, float* gn_part, void* stream) {
-    // 16-byte views: the input is staged in 16-byte LDS-DMA segments; plane limit: H x W x 8 < 2^31
-    const DcvicConvRules rules = {"conv3x3_wino44_ups", Cin, Cout, DCVIC_MAX_SRC, U4_KC, true, DCVIC_OUT_X2, false, false, 1ll << 28};
-    ConvKArgs K;
-    if (const int rc = dcvic_conv_check_io(rules, packed, io, &K)) return rc;
-    DCVIC_CHECK_ARG((io->W & 3) == 0, "conv3x3_wino44_ups: input width must be a multiple of 4");
-    DCVIC_CHECK_ARG(io->act == DCVIC_ACT_NONE || io->act == DCVIC_ACT_RELU || io->act == DCVIC_ACT_LRELU02,
-                    "conv3x3_wino44_ups: activation %d not supported (none / ReLU / LeakyReLU(0.2) only)", io->act);
-    K.gn_part = gn_part;
-    if (const int rc = dcvic_conv_tiles("conv3x3_wino44_ups", &K, U4_KC, U4_CO, U4_TH, U4_TW)) return rc;
-    static std::atomic<unsigned> attr_mask{0};
-    if (DcvicAttrOnce once_{attr_mask})
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wino44_ups_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    conv3x3_wino44_ups_kernel<<<dcvic_persistent_grid(K.nblocks), U4_THREADS, U4_LDS_FLOATS * sizeof(float), (hipStream_t)stream>>>(K);
-    DCVIC_CHECK_LAUNCH("conv3x3_wino44_ups");
-    return DCVIC_OK;
 }

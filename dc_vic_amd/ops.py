@@ -73,7 +73,7 @@ def conv_kernel_name(variant: int) -> str:
     if variant == 9003:
         return "void conv3x3_dma_kernel<3, 3, 4, 96>(ConvKArgs)"
     if variant == 9100:
-        return "void conv3x3_wino_kernel<0>(ConvKArgs)"
+        return "conv3x3_wino_kernel(ConvKArgs)"
     if variant == 9101:
         return "conv3x3_wino_ups_kernel(ConvKArgs)"
     if variant == 9104:

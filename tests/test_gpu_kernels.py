@@ -883,12 +883,12 @@ def test_wino44_eligibility_and_fallbacks(dev):
         return list(ops.kernel_events_stop())
     x = torch.zeros((1, 128, 128, 128), device=dev)
     assert kernel_of(plan, x) == ["conv3x3_wino44_kernel(ConvKArgs)"]
-    assert kernel_of(plan, x, act=ops.ACT_SWISH) == ["void conv3x3_wino_kernel<0>(ConvKArgs)"]       # swish epilogue: F(2x2)
+    assert kernel_of(plan, x, act=ops.ACT_SWISH) == ["conv3x3_wino_kernel(ConvKArgs)"]       # swish epilogue: F(2x2)
     assert "wino" not in kernel_of(plan, torch.zeros((1, 128, 8, 8), device=dev))[0]                   # tiny map: direct kernel
     old = ops.WINO44_ENABLED
     ops.WINO44_ENABLED = False
     try:
-        assert kernel_of(plan, x) == ["void conv3x3_wino_kernel<0>(ConvKArgs)"]
+        assert kernel_of(plan, x) == ["conv3x3_wino_kernel(ConvKArgs)"]
     finally:
         ops.WINO44_ENABLED = old
 
@@ -938,6 +938,50 @@ def test_wino44_fuzz_vs_direct(dev):
         sc = float(yd.abs().max())
         err = float((yd - yw).abs().max()) / max(sc, 1e-6)
         assert err < 1.5e-5, (it, cs, Cout, H, W, N, act, res, err)
+
+
+# route -> (kernel, upsample, F(4x4), output tile rows, batch): 18 workgroup tiles per image on the 8 x 32-pixel tiles, 12 on the 16 x 32
+WINO_FAMILY = {
+    "wino": ("conv3x3_wino_kernel(ConvKArgs)", False, False, 8, 48),
+    "wino_ups": ("conv3x3_wino_ups_kernel(ConvKArgs)", True, False, 8, 48),
+    "wino44": ("conv3x3_wino44_kernel(ConvKArgs)", False, True, 16, 66),
+    "wino44_ups": ("conv3x3_wino44_ups_kernel(ConvKArgs)", True, True, 16, 66),
+}
+
+
+@pytest.mark.parametrize("route", list(WINO_FAMILY))
+def test_wino_family_split_sources_equal_concatenated(dev, route):
+    """The persistent stage stream of the four Winograd kernels (csrc/wino_stream.h) only moves pointers.  So a layer fed three sources
+    gives the same BITS as the same layer fed their concatenation, and an image gives the same bits alone as at the end of a batch in
+    which every workgroup walks an uneven 3 - 4 tiles (the tile count of a workgroup, the bias parity flip, the X stream running ahead
+    into the next image and co-tile).  Sources of 8, 16 and 8 channels (a source switch at every stage but one), Cout = 136 (three
+    co-tiles, the last with 8 live channels), LeakyReLU, a residual on the same-size routes, tiles ragged in both directions."""
+    from dc_vic_amd import ops
+    kernel, ups, f44, th, N = WINO_FAMILY[route]
+    cs, Cout = [8, 16, 8], 136
+    H, W = (10, 20) if ups else (20, 36)
+    Ho, Wo = (2 * H, 2 * W) if ups else (H, W)
+    n_tiles = N * ((Ho + th - 1) // th) * ((Wo + 31) // 32) * ((Cout + 63) // 64)
+    n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+    assert n_tiles > 3 * n_cu and n_tiles % n_cu != 0, (n_tiles, n_cu)
+    x = rnd(N, sum(cs), H, W, seed=901).to(dev)
+    w = rnd(Cout, sum(cs), 3, 3, seed=902, scale=(sum(cs) * 9) ** -0.5).to(dev)
+    b = rnd(Cout, seed=903, scale=0.1).to(dev)
+    r = None if ups else rnd(N, Cout, Ho, Wo, seed=904).to(dev)
+    plan = ops.ConvPlan(w, b, "conv", pad=(1, 1), upsample=ups)
+    plan.wino = "force"
+    plan.wino44 = "force" if f44 else False
+    split = lambda t: [s.contiguous() for s in torch.split(t, cs, dim=1)]
+    ops.kernel_events_start()
+    y = plan(split(x), act=ops.ACT_LRELU02, res=r)
+    y_cat = plan(x, act=ops.ACT_LRELU02, res=r)
+    y_last = plan(split(x[N - 1:]), act=ops.ACT_LRELU02, res=None if r is None else r[N - 1:].contiguous())
+    torch.cuda.synchronize()
+    ev = ops.kernel_events_stop()
+    assert list(ev) == [kernel], list(ev)
+    assert y.shape == (N, Cout, Ho, Wo)
+    assert torch.equal(y, y_cat)
+    assert torch.equal(y[N - 1:], y_last)
 
 
 # ------------------------------------------------------------------------------------------- thin layers (csrc/thin.hip)

@@ -1,4 +1,4 @@
-"""ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h).  The library is REQUIRED: there is no
+"""ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h, include/dcvic_rate.h).  The library is REQUIRED: there is no
 fallback path -- if it is missing or an entry point fails, the caller gets an exception."""
 from __future__ import annotations
 
@@ -103,6 +103,12 @@ SYMBOLS = list(SIGNATURES)
 LOSS_SIGNATURES = {
     "dcvic_focal_ce_workspace_doubles": "q:ii", "dcvic_focal_ce_f32": "i:ppddpppiiip",
 }
+# include/dcvic_rate.h: the differentiable rate term (csrc/rate_train.hip); dcvic_eb_params / dcvic_eb_grads are host structs of 14
+# device pointers (matrix0..4, bias0..4, factor0..3), passed by address
+RATE_SIGNATURES = {
+    "dcvic_gaussian_rate_train_f32": "i:pqppqpqpdpqpqpppqppqpiiip", "dcvic_eb_rate_train_workspace_doubles": "q:iii",
+    "dcvic_eb_rate_train_f32": "i:ppppipdpppppppiiip", "dcvic_eb_aux_loss_f32": "i:pppppiip",
+}
 
 _lib = None
 
@@ -121,7 +127,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python dc_vic_amd/csrc/build.py` "
             "(or __graft_entry__.build()). dc_vic_amd has no fallback path.")
     L = C.CDLL(LIB_PATH)
-    for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
+    for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items(), *RATE_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
         fn = getattr(L, name)                # AttributeError names a symbol the library lacks
         ret, params = sig.split(":")
         fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[c] for c in params]

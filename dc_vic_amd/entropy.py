@@ -7,8 +7,12 @@ Mirror of the reference's wrappers
 which subclass CompressAI 1.2.4 classes (not vendored by the reference).  Here they are
 self-contained: likelihoods / symbols / CDF indexes run as HIP kernels (csrc/rate.hip), CDF tables
 are built once on the host at `update()` time (the reference's codec_setup, hyperprior_dc_vic_model.py:
-65-68) and the rANS coder is the C++ host coder in csrc/host_entropy.cpp.  Inference only (the
-training-time noise / STE branches raise).
+65-68) and the rANS coder is the C++ host coder in csrc/host_entropy.cpp.
+
+`forward(..., is_train=True)` is the reference's training forward: the STE output (`ste_round(x - m) + m`) and the likelihood of
+the NOISY input `x + u`, `u ~ U(-0.5, 0.5)` given as `noise=` or drawn on the device from `generator` (csrc/rate_train.hip).  The
+modules return values only; the gradients of the rate term are the tape ops `gaussian_rate`, `eb_rate` and `eb_aux_loss` of
+train/autograd.py, which run the same kernels.
 
 Parameter and buffer names follow CompressAI 1.2.4 so reference checkpoints load
 (SURVEY App-B / App-E): `_matrix{i}`, `_bias{i}`, `_factor{i}`, `quantiles`, `_offset`,
@@ -68,6 +72,15 @@ def pack_entropy_bottleneck(sd: Dict[str, Tensor], prefix: str):
     med = g("quantiles")[:, 0, 1].contiguous()
     assert mats.shape[1] == 33 and biases.shape[1] == 13 and factors.shape[1] == 12
     return mats, biases, factors, med
+
+
+def _train_noise(x: Tensor, noise: Optional[Tensor], generator: Optional[torch.Generator]) -> Tensor:
+    """The additive quantisation noise of the training forward: `noise` as given, else U(-0.5, 0.5) drawn on x's device."""
+    if noise is None:
+        return torch.rand(x.shape, dtype=torch.float32, device=x.device, generator=generator) - 0.5
+    if noise.shape != x.shape:
+        raise ValueError(f"noise {tuple(noise.shape)} against the input {tuple(x.shape)}")
+    return noise
 
 
 class _TableOwner(nn.Module):
@@ -146,15 +159,29 @@ class EntropyBottleneck(_TableOwner):
             self._packs_key = key
         return self._packs
 
-    # -- eval forward (entropy_bottleneck.py:13-16 -> CompressAI forward(training=False))
-    def forward(self, x: Tensor, is_train: bool = False, bits_out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
-        if is_train:
-            raise NotImplementedError("dc_vic_amd implements the inference path only")
+    def raw_params(self) -> List[Tensor]:
+        """The 14 raw parameter tensors in the order csrc/rate_train.hip takes them (it applies softplus / tanh itself)."""
+        from .train.kernels import EB_PARAM_NAMES
+        return [getattr(self, name).data for name in EB_PARAM_NAMES]
+
+    # -- forward (entropy_bottleneck.py:13-28 -> CompressAI forward(training=is_train)); is_train: STE output, noisy likelihood
+    def forward(self, x: Tensor, is_train: bool = False, bits_out: Optional[Tensor] = None, noise: Optional[Tensor] = None,
+                generator: Optional[torch.Generator] = None) -> Tuple[Tensor, Tensor]:
         x = x.contiguous()
         x_hat = torch.empty_like(x)
         lik = torch.empty_like(x)
+        if is_train:
+            from .train import kernels as K
+            K.eb_rate_train(x, _train_noise(x, noise, generator), self.raw_params(), self.quantiles.data[:, 0, 1], None, 1.0, z_hat=x_hat, lik=lik,
+                            bits=bits_out)
+            return x_hat, lik
         ops.eb_rate(x, self.packs(), x_hat, None, lik, bits_out)
         return x_hat, lik
+
+    def loss(self) -> Tensor:
+        """CompressAI EntropyBottleneck.loss(): sum |logits(quantiles) - target| (1-element device tensor)."""
+        from .train import kernels as K
+        return K.eb_aux_loss(self.raw_params(), self.quantiles.data, self.target)
 
     def symbols(self, x: Tensor) -> Tuple[Tensor, Tensor]:
         x = x.contiguous()
@@ -270,12 +297,15 @@ class GaussianMeanScaleConditional(_TableOwner):
         return self.scale_table
 
     # forward(y, params, is_train) -> (y_hat, likelihood)      ste_gaussian_conditional.py:16-23
-    def forward(self, y: Tensor, params: Tensor, is_train: bool = False, bits_out: Optional[Tensor] = None):
-        if is_train:
-            raise NotImplementedError("dc_vic_amd implements the inference path only")
+    def forward(self, y: Tensor, params: Tensor, is_train: bool = False, bits_out: Optional[Tensor] = None, noise: Optional[Tensor] = None,
+                generator: Optional[torch.Generator] = None):
         mean, std = params.chunk(2, 1)
         y_hat = torch.empty(y.shape, dtype=torch.float32, device=y.device)
         lik = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+        if is_train:
+            from .train import kernels as K
+            K.gaussian_rate_train(y, mean, std, _train_noise(y, noise, generator), None, 1.0, y_hat=y_hat, lik=lik, bits=bits_out)
+            return y_hat, lik
         ops.gaussian_rate(y, None, mean, std, self._table_dev(y), y_hat, None, None, lik, bits_out)
         return y_hat, lik
 

@@ -7,4 +7,4 @@ from .autograd import Ctx, ParamGroup, Var  # noqa: F401
 from .nets import DualBetaCondTamingNLayerDiscriminator  # noqa: F401
 from .trainer import (Adam, DualBetaCondGanDistortionVqCodeTrainer, DualBetaCondOasisGanDistortionVqFusionTrainer, MultiStepLR,  # noqa: F401
                       OasisGANLoss, allreduce_mean_, sample_beta_grid)
-from .losses import CrossEntropyLoss, FocalCrossEntropyLoss, read_loss_section  # noqa: F401
+from .losses import CrossEntropyLoss, FocalCrossEntropyLoss, RateLoss, read_loss_section  # noqa: F401

@@ -493,3 +493,58 @@ def oasis_gan_loss(ctx: Ctx, logits: Var, target: Tensor, is_real: bool, weight:
     if dl is not None:
         acc(logits, dl)
     return (val, score) if want_score else val
+
+
+# ------------------------------------------------------------------------------------------- the rate term (csrc/rate_train.hip)
+def gaussian_rate(ctx: Ctx, y: Var, mu: Var, sigma: Var, noise: Tensor, weights: Optional[Tensor], scale: float, bits: Optional[Tensor],
+                  loss: Optional[Tensor], dy_out: Optional[Tensor] = None) -> Var:
+    """The rate term of one Gaussian-conditional call (GaussianConditional.forward(training=True), ste_gaussian_conditional.py:16-23) in
+    one pass: bits[n] += -log2 of image n's noisy likelihoods, loss[0] += sum_n scale * weights[n] * bits[n] (both accumulate: the
+    caller zeroes them), and that loss term's gradients are seeded into `y`, `mu` and `sigma` now.  With `dy_out` (a [N, C, H, W] view,
+    e.g. a CHARM slice of one 192-channel gradient) the gradient w.r.t. y is written there instead and the caller seeds the parent
+    once.  Returns y_hat = ste_round(y - mu) + mu: a gradient arriving on it goes to `y` unchanged and not to `mu`."""
+    new = lambda: torch.empty(y.shape, dtype=torch.float32, device=y.data.device)
+    out = Var(new(), needs_grad=y.needs_grad)
+    dy = dy_out if dy_out is not None else (new() if y.needs_grad else None)
+    dmu, dsigma = (new() if mu.needs_grad else None), (new() if sigma.needs_grad else None)
+    K.gaussian_rate_train(y.data, mu.data, sigma.data, noise, weights, scale, y_hat=out.data, bits=bits, loss=loss, dy=dy, dmu=dmu,
+                          dsigma=dsigma)
+    if dy is not None and dy_out is None:
+        acc(y, dy)
+    if dmu is not None:
+        acc(mu, dmu)
+    if dsigma is not None:
+        acc(sigma, dsigma)
+
+    def back():
+        if out.grad is not None:
+            acc(y, out.grad)
+    ctx.tape.append(back)
+    return out
+
+
+def eb_rate(ctx: Ctx, z: Var, eb, noise: Tensor, weights: Optional[Tensor], scale: float, bits: Optional[Tensor], loss: Optional[Tensor]) -> Var:
+    """The rate term of the entropy bottleneck `eb` (EntropyBottleneck.forward(training=True)): bits / loss as in gaussian_rate; the
+    loss term's gradient is seeded into `z` and, when `eb`'s parameters belong to one of ctx's groups, added to their views of the flat
+    gradient buffer.  Returns z_hat = ste_round(z - medians) + medians: its gradient goes to `z` unchanged, none to the medians."""
+    zd = _dense(z.data)
+    out = Var(torch.empty_like(zd), needs_grad=z.needs_grad)
+    grads = [ctx.pgrad(getattr(eb, name)) for name in K.EB_PARAM_NAMES]
+    grads = None if any(g is None for g in grads) else grads
+    dz = torch.empty_like(zd) if z.needs_grad else None
+    K.eb_rate_train(zd, _dense(noise), eb.raw_params(), eb.quantiles.data[:, 0, 1], weights, scale, z_hat=out.data, bits=bits, loss=loss, dz=dz,
+                    grads=grads)
+    if dz is not None:
+        acc(z, dz)
+
+    def back():
+        if out.grad is not None:
+            acc(z, out.grad)
+    ctx.tape.append(back)
+    return out
+
+
+def eb_aux_loss(ctx: Ctx, eb) -> Tensor:
+    """EntropyBottleneck.loss(): sum |logits(quantiles) - target| as a 1-element device tensor; its gradient reaches `quantiles` only
+    (added to the flat gradient buffer when `quantiles` belongs to one of ctx's groups)."""
+    return K.eb_aux_loss(eb.raw_params(), eb.quantiles.data, eb.target, ctx.pgrad(eb.quantiles), accumulate=True)

@@ -1,8 +1,9 @@
-"""ctypes wrappers of the training-step kernels (csrc/train.hip, include/dcvic.h "Training step").  torch only
-supplies device memory; every computation is a HIP kernel launch on the current stream."""
+"""ctypes wrappers of the training-step kernels (csrc/train.hip, include/dcvic.h "Training step"; csrc/chan_ce.hip; csrc/rate_train.hip,
+include/dcvic_rate.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
 from __future__ import annotations
 
-from typing import Optional
+import ctypes
+from typing import Optional, Sequence
 
 import torch
 
@@ -157,6 +158,83 @@ def focal_ce(logits: Tensor, target: Tensor, gamma: float, scale: float, want_gr
     N, Cc, HW, ws, loss, dl = _chan_ce_buffers("focal_ce", lib().dcvic_focal_ce_workspace_doubles, logits, target, want_grad)
     check(lib().dcvic_focal_ce_f32(_p(logits), _p(target), float(gamma), scale, _p(loss), _p(dl), _p(ws), N, Cc, HW, _stream()), "focal_ce")
     return loss, dl
+
+
+# ------------------------------------------------------------------------------------------- the rate term (csrc/rate_train.hip)
+EB_PARAM_NAMES = tuple(f"_matrix{i}" for i in range(5)) + tuple(f"_bias{i}" for i in range(5)) + tuple(f"_factor{i}" for i in range(4))
+_EB_WIDTH = (3, 9, 9, 9, 3, 3, 3, 3, 3, 1, 3, 3, 3, 3)
+
+
+def _flat_f32(t: Optional[Tensor], n: int, what: str) -> Optional[Tensor]:
+    """`t` (or None) checked to be a contiguous fp32 device tensor of n values."""
+    if t is not None and (t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != n):
+        raise ValueError(f"{what} must be a contiguous fp32 device tensor of {n} value(s), got {t.dtype} {tuple(t.shape)} {t.device}")
+    return t
+
+
+def _eb_struct(tensors: Optional[Sequence[Tensor]], C: int, what: str):
+    """dcvic_eb_params / dcvic_eb_grads: 14 device pointers in the order of EB_PARAM_NAMES (a host struct, passed by address)."""
+    if tensors is None:
+        return None
+    if len(tensors) != 14:
+        raise ValueError(f"{what}: 14 tensors (matrix0..4, bias0..4, factor0..3), got {len(tensors)}")
+    for t, k, name in zip(tensors, _EB_WIDTH, EB_PARAM_NAMES):
+        _flat_f32(t, C * k, f"{what}: {name}")
+    return (ctypes.c_void_p * 14)(*[t.data_ptr() for t in tensors])
+
+
+def gaussian_rate_train(y: Tensor, mu: Tensor, sigma: Tensor, noise: Tensor, weights: Optional[Tensor], scale: float, y_hat: Optional[Tensor] = None,
+                        lik: Optional[Tensor] = None, bits: Optional[Tensor] = None, loss: Optional[Tensor] = None, dy: Optional[Tensor] = None,
+                        dmu: Optional[Tensor] = None, dsigma: Optional[Tensor] = None) -> None:
+    """dcvic_gaussian_rate_train_f32 on [N, C, H, W] views (each with its own batch stride; mu / sigma and dmu / dsigma share one):
+    bits [N] and loss [1] ACCUMULATE, every other given output is overwritten."""
+    N, Cc, H, W = _chk4(y, "gaussian_rate_train y")
+    for t, name in ((mu, "mu"), (sigma, "sigma"), (noise, "noise"), (y_hat, "y_hat"), (lik, "lik"), (dy, "dy"), (dmu, "dmu"), (dsigma, "dsigma")):
+        if t is not None and _chk4(t, f"gaussian_rate_train {name}") != (N, Cc, H, W):
+            raise ValueError(f"gaussian_rate_train: {name} {tuple(t.shape)} against y {tuple(y.shape)}")
+    if _bs(mu) != _bs(sigma) or (dmu is not None and dsigma is not None and _bs(dmu) != _bs(dsigma)):
+        raise ValueError("gaussian_rate_train: mu / sigma (and dmu / dsigma) must share a batch stride")
+    ws = None
+    if bits is not None or loss is not None:
+        ws = _workspace(N * int(lib().dcvic_rate_blocks(Cc * H * W)), y.device, "rate_train", torch.float64)
+    check(lib().dcvic_gaussian_rate_train_f32(_p(y), _bs(y), _p(mu), _p(sigma), _bs(mu), _p(noise), _bs(noise), _p(_flat_f32(weights, N, "gaussian_rate_train: sample weights")),
+                                              float(scale), _p(y_hat), _bs(y_hat), _p(lik), _bs(lik), _p(_flat_f32(bits, N, "gaussian_rate_train: bits")),
+                                              _p(_flat_f32(loss, 1, "gaussian_rate_train: loss")), _p(dy), _bs(dy), _p(dmu), _p(dsigma),
+                                              _bs(dmu if dmu is not None else dsigma), _p(ws), N, Cc, H * W, _stream()), "gaussian_rate_train")
+
+
+def eb_rate_train(z: Tensor, noise: Tensor, params: Sequence[Tensor], medians: Tensor, weights: Optional[Tensor], scale: float,
+                  z_hat: Optional[Tensor] = None, lik: Optional[Tensor] = None, bits: Optional[Tensor] = None, loss: Optional[Tensor] = None,
+                  dz: Optional[Tensor] = None, grads: Optional[Sequence[Tensor]] = None) -> None:
+    """dcvic_eb_rate_train_f32 on contiguous [N, C, H, W]: `params` are the 14 RAW parameter tensors in the order of EB_PARAM_NAMES,
+    `medians` a [C] view (quantiles[:, 0, 1]); bits, loss and the 14 `grads` ACCUMULATE, every other given output is overwritten."""
+    N, Cc, H, W = _chk4(z, "eb_rate_train z")
+    for t, name in ((z, "z"), (noise, "noise"), (z_hat, "z_hat"), (lik, "lik"), (dz, "dz")):
+        if t is not None and (_chk4(t, f"eb_rate_train {name}") != (N, Cc, H, W) or not t.is_contiguous()):
+            raise ValueError(f"eb_rate_train: {name} must be contiguous {tuple(z.shape)}")
+    if medians.dtype != torch.float32 or not medians.is_cuda or medians.dim() != 1 or medians.numel() != Cc:
+        raise ValueError(f"eb_rate_train: medians must be a [C] fp32 device view, got {tuple(medians.shape)}")
+    ps, gs = _eb_struct(params, Cc, "eb_rate_train params"), _eb_struct(grads, Cc, "eb_rate_train grads")
+    ws = None
+    if bits is not None or loss is not None:
+        ws = _workspace(int(lib().dcvic_eb_rate_train_workspace_doubles(N, Cc, H * W)), z.device, "eb_rate_train", torch.float64)
+    check(lib().dcvic_eb_rate_train_f32(_p(z), _p(noise), ctypes.addressof(ps), _p(medians), max(1, medians.stride(0)), _p(_flat_f32(weights, N, "eb_rate_train: sample weights")),
+                                        float(scale), _p(z_hat), _p(lik), _p(_flat_f32(bits, N, "eb_rate_train: bits")), _p(_flat_f32(loss, 1, "eb_rate_train: loss")),
+                                        _p(dz), ctypes.addressof(gs) if gs is not None else None, _p(ws), N, Cc, H * W, _stream()), "eb_rate_train")
+
+
+def eb_aux_loss(params: Sequence[Tensor], quantiles: Tensor, target: Tensor, dquantiles: Optional[Tensor] = None, accumulate: bool = False,
+                want_value: bool = True) -> Optional[Tensor]:
+    """dcvic_eb_aux_loss_f32: the value (1-element device tensor, or None) of EntropyBottleneck.loss(); its gradient w.r.t. `quantiles`
+    [C, 1, 3] is written (or, with accumulate, added) to `dquantiles` when given."""
+    Cc = quantiles.shape[0]
+    for t, n, name in ((quantiles, 3 * Cc, "quantiles"), (target, 3, "target"), (dquantiles, 3 * Cc, "dquantiles")):
+        _flat_f32(t, n, f"eb_aux_loss: {name}")
+    ps = _eb_struct(params, Cc, "eb_aux_loss params")
+    aux = torch.empty(1, dtype=torch.float32, device=quantiles.device) if want_value else None
+    check(lib().dcvic_eb_aux_loss_f32(ctypes.addressof(ps), _p(quantiles), _p(target), _p(aux), _p(dquantiles), 1 if accumulate else 0, Cc, _stream()),
+          "eb_aux_loss")
+    return aux
 
 
 def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, b1: float, b2: float, eps: float, step: int, gscale: Optional[Tensor]) -> None:

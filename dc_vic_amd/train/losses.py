@@ -57,6 +57,40 @@ class FocalCrossEntropyLoss:
         return A.focal_cross_entropy_loss(ctx, logits, target, self.loss_weight, self.gamma, self.reduction)
 
 
+@LOSS_REGISTRY.register()
+class RateLoss:
+    """rate_loss.py:11-24: loss_weight * reduce(bpp).  The rate kernels (csrc/rate_train.hip) form sum_n scale * w[n] * bits[n]
+    themselves, so this class states the trainers' expressions as the per-sample weight vector w (with scale = 1):
+      RateDistortionVqCodeTrainer: bpp is the scalar sum(bits) / (N * num_pixel), every reduction leaves it as it is:
+        loss_weight * sum(bits) / (N * num_pixel)
+      DualBetaCondRateDistortionVqCodeTrainer with sample_beta_batch (dual_cond_rate_distortion_vq_code_trainer.py:92-108,167-175):
+        bpp[n] = bits[n] / num_pixel (_calc_batch_bpp), then apply_loss_weight's (loss * beta_weight).mean() with
+        beta_weight = exp(beta_rate) or beta_rate + offset:
+          none: mean_n(loss_weight * bpp[n] * beta_weight[n]);  mean / sum: loss_weight * mean(bpp) or sum(bpp), times mean(beta_weight)
+    `target_rate` is accepted and unused, as in the reference."""
+
+    def __init__(self, loss_weight: float, target_rate: float = 0.0, reduction: str = "mean", **extra):
+        if extra:
+            raise ValueError(f"RateLoss: unknown keyword(s) {sorted(extra)}")
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"reduction: {reduction} is unknown; use mean, sum or none")
+        self.loss_weight, self.target_rate, self.reduction = float(loss_weight), float(target_rate), reduction
+
+    def sample_weights(self, N: int, num_pixel: int, beta_weight: Optional[Tensor] = None, device=None) -> Tensor:
+        """The fp32 [N] vector w with sum_n w[n] * bits[n] equal to the trainer's rate loss (on `device`, default beta_weight's)."""
+        import torch
+        if beta_weight is None:
+            return torch.full((N,), self.loss_weight / (N * num_pixel), dtype=torch.float32, device=device)
+        if beta_weight.dim() != 1 or beta_weight.numel() != N:
+            raise ValueError(f"beta_weight: a vector of {N} per-sample weights, got {tuple(beta_weight.shape)}")
+        b = beta_weight.to(device=device if device is not None else beta_weight.device, dtype=torch.float64)
+        if self.reduction == "none":
+            w = b * (self.loss_weight / (N * num_pixel))
+        else:
+            w = (b.mean() * (self.loss_weight / (num_pixel * (N if self.reduction == "mean" else 1)))).expand(N)
+        return w.to(torch.float32).contiguous()
+
+
 # ---------------------------------------------------------------------------------------------------- the YAML's `loss` section
 # the reference's trainers with a rate term and per-sample beta weights (config/exp1_stage1_1.yaml, exp1_stage1_2.yaml): not built,
 # scripts/train.py refuses them by `trainer.type`.  Their `rate_loss` entry and `reduction: none` are those trainers' business and

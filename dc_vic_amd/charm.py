@@ -43,7 +43,7 @@ class SliceTransform(nn.Module):
         """First conv restricted to input channels [n_lead:] (the leading hyperprior channels are handled by a
         stacked launch, see Minnen20CharmContextModel._hyper_partials); None when nothing is left."""
         c0 = self.model[0]
-        key = (c0.weight.data_ptr(), c0.weight._version, n_lead)
+        key = (c0.weight.data_ptr(), c0.weight._version, c0.bias.data_ptr(), n_lead)     # (the plan reads the bias in place)
         if getattr(self, "_rest_key", None) != key:
             w = c0.weight.detach()
             self._rest = ops.ConvPlan(w[:, n_lead:].contiguous(), c0.bias, "conv", pad=(2, 2)) if w.shape[1] > n_lead else None

@@ -33,7 +33,7 @@ from .elic import ElicDualBetaFtFeatFusionDecoder, ElicDualBetaFtVqScEncoder  # 
 from .entropy import EntropyBottleneck, GaussianMeanScaleConditional, get_scale_table, host_threads
 from .fusion import build_vq_fusion_module
 from .hyperprior import Minnen20HyperDecoder, Minnen20HyperEncoder  # noqa: F401
-from .layers import allow_bf16
+from .layers import WeightFingerprint, allow_bf16, invalidate_weight_caches
 from .registry import (CONTEXTMODEL_REGISTRY, DECODER_REGISTRY, ENCODER_REGISTRY, ENTROPYMODEL_REGISTRY,
                        HYPERDECODER_REGISTRY, HYPERENCODER_REGISTRY, LRP_REGISTRY, MODEL_REGISTRY, VQ_ESTIMATOR_REGISTRY)
 from .swin import DualBlockSwinVqEstimator  # noqa: F401
@@ -80,7 +80,8 @@ class _GraphCache:
     replay).  Same kernels, same arguments: results are bit-identical to the eager path (tested).
     Policy: a (segment, input shapes, conditioning) key is captured the SECOND time it is seen (`capture_after`; a folder of images that
     all differ in size stays eager: a capture costs two extra passes), up to `max_pixels` per call and `max_entries` graphs (LRU).
-    Captures that fail (unsupported call inside the segment) fall back to the eager path for good.  On by default since round 3
+    Captures that fail (unsupported call inside the segment) fall back to the eager path for good.  An entry whose modules' weights are
+    no longer the ones it was captured with is dropped, never replayed (`run`).  On by default since round 3
     (measured 193 -> 200 images/s at batch 32); `DCVIC_GRAPHS=0` switches it off.  Per-launch HIP events (bench.py's roofline steps,
     ops.kernel_events_start) and the stage hook bypass it."""
 
@@ -99,8 +100,16 @@ class _GraphCache:
     def usable(self, n_pixels: int) -> bool:
         return (not self.disabled) and n_pixels <= self.max_pixels and ops._EVENTS is None and STAGE_HOOK is None
 
-    def run(self, key, fn, inputs: Sequence[Tensor], keep=None):
+    def run(self, key, fn, inputs: Sequence[Tensor], keep=None, modules: Sequence[nn.Module] = ()):
+        """`modules`: the modules `fn` runs.  The captured graph holds raw pointers to their packed weights (and to the parameters
+        themselves) of that moment, and nothing per layer runs during a replay, so the entry carries the fingerprint of their
+        parameters and buffers (layers.WeightFingerprint) and is replayed only while it still matches; otherwise it is dropped and the
+        key starts again at its first sighting (eager, which re-packs the layers, then capture)."""
         ent = self.entries.get(key)
+        if ent is not None and ent[4]() != ent[5]:
+            del self.entries[key]
+            self.seen.pop(key, None)
+            ent = None
         if ent is None:
             n = self.seen.get(key, 0) + 1
             if len(self.seen) > 256:
@@ -135,13 +144,14 @@ class _GraphCache:
                     import traceback
                     traceback.print_exc()
                 return fn(*inputs)
-            ent = (graph, static_in, out, keep() if callable(keep) else keep)
+            watch = WeightFingerprint(modules)
+            ent = (graph, static_in, out, keep() if callable(keep) else keep, watch, watch())
             self.entries[key] = ent
             while len(self.entries) > self.max_entries:
                 self.entries.popitem(last=False)
         else:
             self.entries.move_to_end(key)
-        graph, static_in, out, _ = ent
+        graph, static_in, out = ent[:3]
         for s_, t in zip(static_in, inputs):
             s_.copy_(t)
         graph.replay()
@@ -284,11 +294,14 @@ class BaseModel(nn.Module):
 
     def load_state_dict(self, state_dict, strict: bool = True):
         out = super().load_state_dict(state_dict, strict=strict)
-        self._graphs.clear()                   # captured segments hold the old packed weights
-        for m in self.modules():
-            if hasattr(m, "invalidate_caches"):
-                m.invalidate_caches()
+        self.invalidate_weight_caches()
         return out
+
+    def invalidate_weight_caches(self) -> None:
+        """Drop every copy of the weights the model keeps: packed plans, fused packs, cached beta vectors, captured hipGraphs
+        (layers.invalidate_weight_caches).  Weight changes torch versions (load_state_dict on the model or a child, in-place ops on a
+        parameter, a replaced parameter) are detected without it; a `p.data` or raw-pointer write is not -- call this after one."""
+        invalidate_weight_caches(self)
 
     # base_model.py:106-130
     def load_learned_weight(self, ckpt_path: str, strict: bool = False) -> None:
@@ -604,6 +617,13 @@ class HyperpriorDualCondVicModel(HyperpriorVicModel):
                              vq_mse=float(vq_mse[0])))
         return rows
 
+    def _segment_modules(self, segment: str) -> Tuple[nn.Module, ...]:
+        """The modules whose weights the hipGraph segment "enc" (compress_batch) / "dec" (decompress_batch) reads."""
+        vq = self.vq_model
+        if segment == "enc":
+            return (vq.encoder, vq.quant_conv, vq.quantize, self.encoder)
+        return (self.decoder, self.vq_estimator, vq.quantize, vq.post_quant_conv, self.fusion_module, vq.decoder)
+
     # ------------------------------------------------------------------ compress (330-376)
     @torch.no_grad()
     def compress_batch(self, real_images: Tensor, quality_ind: int) -> Dict:
@@ -621,7 +641,8 @@ class HyperpriorDualCondVicModel(HyperpriorVicModel):
                 return idx_, y_
             gt_vq_indices, y = self._graphs.run(("enc", tuple(real_images.shape), quality_ind, float(beta_rate), float(beta_vq)), seg,
                                                 [real_images.to(self.device, dtype=torch.float32).contiguous()],
-                                                keep=lambda: list(self.encoder._vec_cache.values()))
+                                                keep=lambda: list(self.encoder._vec_cache.values()),
+                                                modules=self._segment_modules("enc"))
             gt_vq_indices, y = gt_vq_indices.clone(), y.clone()
         else:
             x = self.img_preprocess(real_images, is_train=False)
@@ -698,7 +719,8 @@ class HyperpriorDualCondVicModel(HyperpriorVicModel):
         elif self._graphs.usable(len(string_lists) * padH * padW):
             fake = self._graphs.run(("dec", tuple(y_hat.shape), q, float(beta_rate), float(beta_vq), self.decoder_precision),
                                     lambda yh: self._decode(yh, w, beta_rate, beta_vq)[0], [y_hat.contiguous()],
-                                    keep=lambda: list(self.decoder._vec_cache.values()))
+                                    keep=lambda: list(self.decoder._vec_cache.values()),
+                                    modules=self._segment_modules("dec"))
         else:
             fake, _ = self._decode(y_hat, w, beta_rate, beta_vq)
         _mark("decode_nn")

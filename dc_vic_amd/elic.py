@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .layers import Act, Conv2d, ConvTranspose2d, Linear
+from .layers import Act, Conv2d, ConvTranspose2d, Linear, WeightFingerprint
 from .registry import DECODER_REGISTRY, ENCODER_REGISTRY
 
 Tensor = torch.Tensor
@@ -141,6 +141,19 @@ class _BetaCond(nn.Module):
         mlp_in = 2 * (2 * L + 1) if include_x else 2 * 2 * L
         self.mlp = nn.Sequential(Linear(mlp_in, cond_ch), Act(), Linear(cond_ch, cond_ch))
         self._vec_cache: Dict = {}
+        self._vec_watch = None       # (ids of the modules the cached vectors came from, their WeightFingerprint, its value then)
+
+    def _vec_cache_current(self, modules: List[BetaScaleShiftModule]) -> None:
+        """The cached vectors are functions of `mlp` and of every scale/shift module passed in: empty the cache when one of those weights
+        is no longer the one the vectors were computed from (layers.WeightFingerprint: same storage, same version)."""
+        ids = tuple(id(m) for m in modules)
+        w = self._vec_watch
+        if w is None or w[0] != ids:
+            w = self._vec_watch = (ids, WeightFingerprint([self.mlp] + list(modules)), None)
+        fp = w[1]()
+        if fp != w[2]:
+            self._vec_cache.clear()
+            self._vec_watch = (ids, w[1], fp)
 
     def cond(self, beta_1, beta_2, device) -> Tensor:
         c = torch.cat([self.embed_1.embed(beta_1), self.embed_2.embed(beta_2)], dim=1).to(device)  # [B, 4L(+2)]
@@ -152,6 +165,7 @@ class _BetaCond(nn.Module):
         scalar = isinstance(beta_1, (int, float)) and isinstance(beta_2, (int, float))
         key = None
         if scalar:
+            self._vec_cache_current(modules)
             key = (float(beta_1), float(beta_2), str(device))
             hit = self._vec_cache.get(key)
             if hit is not None:
@@ -165,7 +179,8 @@ class _BetaCond(nn.Module):
         return vecs
 
     def invalidate_caches(self):
-        """Called after weights change (load_state_dict / .to()): the cached vectors depend on them."""
+        """Called through layers.invalidate_weight_caches after a weight write torch does not version (`p.data`, raw pointer): the cached
+        vectors depend on the weights.  Versioned changes are seen by _vec_cache_current."""
         self._vec_cache.clear()
 
     def _apply(self, fn, *args, **kwargs):

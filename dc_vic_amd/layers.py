@@ -8,6 +8,7 @@ Weights are packed into the MFMA tile layout lazily and re-packed if a parameter
 from __future__ import annotations
 
 import math
+import operator
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -16,6 +17,61 @@ import torch.nn as nn
 from . import ops
 
 Tensor = torch.Tensor
+_VERSION = operator.attrgetter("_version")
+
+
+class WeightFingerprint:
+    """Identity of the weights under some modules: (tensor object, storage address, version) of every parameter and buffer.  It moves
+    when torch can see the change -- load_state_dict, an in-place op on the parameter (p.copy_, p.add_, an optimiser step), a parameter
+    replaced by a new one, .to(device), `p.data = other` -- and does NOT move under a write torch cannot see: `p.data.copy_()` or a
+    raw-pointer write (a HIP kernel on p.data_ptr()) leave p._version where it was.  Those routes need invalidate_weight_caches().
+    The modules' parameter / buffer dicts are gathered once (a replaced submodule is not followed) and read again by every call; the
+    tensors of the last call are held, so a freed parameter's address cannot come back under a new one.  ~0.3 us per tensor."""
+
+    def __init__(self, modules: Sequence[nn.Module]):
+        seen, self._dicts = set(), []
+        for root in modules:
+            for m in root.modules():
+                if id(m) not in seen:
+                    seen.add(id(m))
+                    self._dicts += [d for d in (m._parameters, m._buffers) if d]
+        self._held = []
+
+    def __call__(self) -> tuple:
+        ts = self._held = [t for d in self._dicts for t in d.values() if t is not None]
+        return tuple(map(id, ts)), tuple(map(Tensor.data_ptr, ts)), tuple(map(_VERSION, ts))
+
+
+# Every cache in the package that holds a copy of (or a pointer into a copy of) some weights, by the attribute it lives in on its module,
+# with the value that means "empty".  A new cache goes in here: invalidate_weight_caches is the one place that drops them all.
+WEIGHT_CACHE_ATTRS = {
+    "_plan": None,          # _Packed: the packed ConvPlan (also fid.FrozenConv)
+    "_plain_plan": None,    # train/autograd.conv: the fp32 plan of a frozen layer
+    "_dgrad": None,         # train/autograd.conv: the data-gradient plan (flipped / transposed copy)
+    "_qkv_plan": None,      # vqgan.AttnBlock: q/k/v as one convolution
+    "_rest_key": None,      # charm.SliceTransform: first conv without its hyperprior channels
+    "_rest": None,
+    "_hp_key": None,        # charm.Minnen20CharmContextModel: stacked hyperprior partial convolutions
+    "_hp_mean": None,
+    "_hp_scale": None,
+    "_packs": None,         # entropy.EntropyBottleneck: softplus / tanh'd matrices
+}
+
+
+def invalidate_weight_caches(module: nn.Module) -> None:
+    """Drop everything derived from the weights under `module`: packed convolution plans, fused q/k/v packs, CHARM's split plans, the
+    entropy bottleneck's packs, cached beta vectors (`_vec_cache`) and captured hipGraphs (`_graphs`).  Needed after a write torch does
+    not version (`p.data` / raw pointer, e.g. the fused Adam kernel); every torch-visible route is detected without it
+    (WeightFingerprint).  The integer CDF tables of the entropy models are state, not cache: they are rebuilt by codec_setup()."""
+    for m in module.modules():
+        d = m.__dict__
+        for name, empty in WEIGHT_CACHE_ATTRS.items():
+            if d.get(name, empty) is not empty:
+                d[name] = empty
+        if "_vec_cache" in d:
+            m.invalidate_caches()
+        if "_graphs" in d:
+            m._graphs.clear()
 
 
 class _Packed(nn.Module):

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..layers import Conv2d, ConvTranspose2d, GroupNorm, LayerNormC, Linear
+from ..layers import Conv2d, ConvTranspose2d, GroupNorm, LayerNormC, Linear, invalidate_weight_caches
 from . import kernels as K
 
 Tensor = torch.Tensor
@@ -76,20 +76,10 @@ class ParamGroup:
 
     def refresh_plans(self) -> None:
         """The flat buffer was updated in place (Adam kernel): cached packed weights / beta vectors are stale."""
+        # (a whole model in the group: its captured hipGraphs hold the old packed weights; a module that was NOT trainable in some Ctx --
+        # the discriminator inside the generator step -- cached a flipped / transposed COPY of its weights as its data-gradient plan)
         for mod in self.modules:
-            for m in mod.modules():
-                if hasattr(m, "_graphs"):
-                    m._graphs.clear()          # (a whole model in the group: its captured hipGraphs hold the old packed weights)
-                if hasattr(m, "_plan"):
-                    m._plan = None
-                if hasattr(m, "_qkv_plan"):
-                    m._qkv_plan = None
-                if getattr(m, "_dgrad", None) is not None:
-                    # data-gradient plan cached while this module was NOT trainable in some Ctx (the discriminator inside the
-                    # generator step): it holds a flipped / transposed COPY of the weights, stale once Adam moved them
-                    m._dgrad = None
-                if hasattr(m, "invalidate_caches"):
-                    m.invalidate_caches()
+            invalidate_weight_caches(mod)
 
 
 class Ctx:

@@ -293,6 +293,49 @@ def test_determinism_batch_invariance_and_graph_cache(model):
     assert torch.equal(c32, a32)
 
 
+def test_precision_switch_after_a_weight_change(model):
+    """Graphs of both precisions captured, then one decoder convolution (a layer that does run on the bf16 kernel) updated in place: the
+    switch to bf16 and back must not replay either graph, which hold the fp32 route packs and the bf16 pack of the OLD weights.  Both
+    results equal their eager decode on the new weights, and both moved."""
+    from dc_vic_amd.comp_model import BF16_KEEP_FP32
+    name = "vq_model.decoder.up.1.block.0.conv1"
+    assert name not in BF16_KEEP_FP32
+    conv = model.get_submodule(name)
+    g = model._graphs
+    was = g.disabled
+    xs = torch.rand((2, 3, 64, 64), generator=torch.Generator().manual_seed(10)) * 2 - 1
+    w_before = conv.weight.detach().clone()
+    try:
+        model.set_decoder_precision("fp32")
+        streams = model.compress_batch(xs, 0)["string_lists"]
+        old = {}
+        for prec in ("fp32", "bf16"):
+            model.set_decoder_precision(prec)
+            for _ in range(3):                                 # eager, capture, replay
+                old[prec] = model.decompress_batch(streams)[0].clone()
+        assert {k[-1] for k in g.entries if k[0] == "dec"} == {"fp32", "bf16"}, list(g.entries)
+        model.set_decoder_precision("fp32")
+        with torch.no_grad():
+            noise = torch.randn(conv.weight.shape, generator=torch.Generator().manual_seed(11)) * float(conv.weight.std())
+            conv.weight.add_(noise.to(DEV))
+        new = {}
+        for prec in ("bf16", "fp32"):                          # to bf16 and back
+            model.set_decoder_precision(prec)
+            new[prec] = model.decompress_batch(streams)[0].clone()
+        g.disabled = True
+        for prec in ("bf16", "fp32"):
+            model.set_decoder_precision(prec)
+            eager = model.decompress_batch(streams)[0]
+            assert torch.equal(new[prec], eager), f"{prec}: a graph captured with the old weights was replayed"
+            assert not torch.equal(new[prec], old[prec]), prec
+        assert not torch.equal(new["bf16"], new["fp32"])
+    finally:
+        g.disabled = was
+        with torch.no_grad():
+            conv.weight.copy_(w_before)
+        model.set_decoder_precision("fp32")
+
+
 def test_default_is_fp32_and_unknown_precision_raises(model):
     fresh = _new_model()
     assert fresh.decoder_precision == "fp32"

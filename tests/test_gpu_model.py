@@ -358,6 +358,31 @@ def test_roundtrip_bit_exact_256(model):
         assert 0.85 * pred - 256 < real_bits < 1.10 * pred + 256, (real_bits, pred)
 
 
+def test_batch_invariance_at_32(model):
+    """The benchmark's batch size, graph path included (default policy: eager, capture, replay): the bytes do not depend on which of the
+    three ran, an image coded alone gives the bytes and the reconstruction it gives inside the batch of 32 -- what lets a decoder in one
+    batch read a stream written in another -- and the decoder reproduces the encoder's latents bit for bit."""
+    assert not model._graphs.disabled and model._graphs.capture_after == 2
+    x = img((32, 3, 256, 256), 110)
+    r = model.compress_batch(x, 0)
+    for _ in range(2):
+        assert model.compress_batch(x, 0)["string_lists"] == r["string_lists"]
+    assert ("enc", (32, 3, 256, 256)) in {k[:2] for k in model._graphs.entries}
+    imgs = None
+    for _ in range(3):
+        out, z_hat, y_hat = model.decompress_batch(r["string_lists"])
+        assert torch.equal(y_hat, r["y_hat"]) and torch.equal(z_hat, r["z_hat"])
+        assert imgs is None or torch.equal(out, imgs)
+        imgs = out.clone()
+    assert "dec" in {k[0] for k in model._graphs.entries} and not model._graphs.disabled
+    assert imgs.shape == (32, 3, 256, 256)
+    for k in (0, 13, 31):
+        r1 = model.compress(x[k:k + 1], 0)
+        assert r1["string_list"] == r["string_lists"][k], k
+        i1, _, _ = model.decompress(r["string_lists"][k])
+        assert torch.equal(i1[0], imgs[k]), k
+
+
 def test_ragged_and_kodak_shape(model):
     """Non-multiple-of-64 image (reflect pad + crop) and the Kodak shape 512x768 round-trip."""
     for shape, q in (((1, 3, 100, 70), 4), ((1, 3, 512, 768), 2)):

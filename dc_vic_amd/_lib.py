@@ -1,4 +1,4 @@
-"""ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h, include/dcvic_rate.h).  The library is REQUIRED: there is no
+"""ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h, include/dcvic_rate.h, include/dcvic_train.h).  The library is REQUIRED: there is no
 fallback path -- if it is missing or an entry point fails, the caller gets an exception."""
 from __future__ import annotations
 
@@ -109,6 +109,10 @@ RATE_SIGNATURES = {
     "dcvic_gaussian_rate_train_f32": "i:pqppqpqpdpqpqpppqppqpiiip", "dcvic_eb_rate_train_workspace_doubles": "q:iii",
     "dcvic_eb_rate_train_f32": "i:ppppipdpppppppiiip", "dcvic_eb_aux_loss_f32": "i:pppppiip",
 }
+# include/dcvic_train.h: training-step entry points added after dcvic.h's table was frozen (csrc/train.hip)
+TRAIN_SIGNATURES = {
+    "dcvic_conv_wgrad_src_f32": "i:pqiiipqiiiiiiiiipiiipp",
+}
 
 _lib = None
 
@@ -127,7 +131,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python dc_vic_amd/csrc/build.py` "
             "(or __graft_entry__.build()). dc_vic_amd has no fallback path.")
     L = C.CDLL(LIB_PATH)
-    for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items(), *RATE_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
+    for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items(), *RATE_SIGNATURES.items(), *TRAIN_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
         fn = getattr(L, name)                # AttributeError names a symbol the library lacks
         ret, params = sig.split(":")
         fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[c] for c in params]

@@ -3,11 +3,13 @@
 // Forward kernels are the inference ones; data-gradients of convolutions reuse them too (the adjoint of a convolution is a
 // convolution with transposed / flipped weights, of a stride-2 transposed convolution a stride-2 convolution).  New here:
 //   conv_wgrad      dW = sum_pixels dY (x) X   -- fp32 MFMA, split over pixel slabs, slab partials reduced in a FIXED order
+//                   (conv_wgrad_src: the same for ONE channel-slice source of a multi-source convolution, include/dcvic_train.h)
 //   groupnorm / layernorm backward (+ fused swish), activation and gate backwards, per-channel reductions,
 //   column-softmax backward (attention), Swin window-attention backward, MSE / BCE-with-logits / cross-entropy with
 //   gradients, Adam, deterministic sum of squares (gradient clipping).
 // Everything is deterministic: no atomics, reductions in a layer-defined order (DDP ranks and reruns agree bit for bit).
 #include "common.h"
+#include "dcvic_train.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -41,7 +43,7 @@ __device__ __forceinline__ double bsum_d(double v, double* red) {
 // both operands have the contraction index contiguous in memory, so the LDS images are [row][pix] with ODD row strides and
 // the MFMA 32x32x2 operand reads (lane -> row, lane half -> pixel parity) are conflict-free.
 // Workgroup = (m block of 128, c block of 32, ky, pixel slab); 4 waves, wave w owns rows 32 w .. 32 w + 31 and KW accumulators.
-// Partials [slab][m][c][ky][kx] are reduced by wgrad_reduce_kernel in ascending slab order.
+// Partials [slab][m][c][ky][kx] are reduced by slab_reduce_kernel in ascending slab order.
 __device__ __attribute__((aligned(16))) float dcvic_train_zero[4];   // zero-initialised: source of out-of-range elements
 
 struct WgradArgs {
@@ -196,13 +198,16 @@ __global__ __launch_bounds__(256, KHT > 1 ? 2 : 1) void conv_wgrad_kernel(const 
     }
 }
 
-// out[i] (+)= sum_s part[s][i], s ascending
-__global__ void slab_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, long long len, int slabs, int accumulate) {
+// out[o(i)] (+)= sum_s part[s][i], s ascending.  part rows of `row` elements land in out rows of `out_row` elements at `out_off`:
+// o(i) = (i / row) * out_row + out_off + i % row  (dense: row = out_row, out_off = 0 -> o(i) = i)
+__global__ void slab_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, long long len, int slabs, int accumulate,
+                                   long long row, long long out_row, long long out_off) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= len) return;
-    float s = accumulate ? out[i] : 0.f;
+    const long long o = row == out_row ? i + out_off : (i / row) * out_row + out_off + i % row;
+    float s = accumulate ? out[o] : 0.f;
     for (int k = 0; k < slabs; ++k) s += part[(long long)k * len + i];
-    out[i] = s;
+    out[o] = s;
 }
 
 extern "C" long long dcvic_conv_wgrad_workspace_floats(int N, int M, int Cx, int KH, int KW, int Hg, int* slabs_out) {
@@ -220,15 +225,19 @@ extern "C" long long dcvic_conv_wgrad_workspace_floats(int N, int M, int Cx, int
     return (long long)N * per_img * M * Cx * KH * KW;
 }
 
-extern "C" int dcvic_conv_wgrad_f32(const float* G, long long g_bs, int M, int Hg, int Wg, const float* X, long long x_bs, int Cx, int Hx,
-                                    int Wx, int N, int KH, int KW, int stride, int pt, int pl, float* dW, int accumulate, float* workspace,
-                                    void* stream) {
-    DCVIC_CHECK_ARG(G && X && dW && workspace, "conv_wgrad: null pointer");
-    DCVIC_CHECK_ARG(KW >= 1 && KW <= 5 && KH >= 1 && KH <= 5 && stride >= 1 && stride <= 4, "conv_wgrad: kernel %dx%d stride %d unsupported", KH, KW, stride);
-    DCVIC_CHECK_ARG(N > 0 && M > 0 && Cx > 0 && Hg > 0 && Wg > 0 && Hx > 0 && Wx > 0, "conv_wgrad: empty map N=%d M=%d Cx=%d Hg=%d Wg=%d Hx=%d Wx=%d",
-                    N, M, Cx, Hg, Wg, Hx, Wx);
+// One source of `Cx` channels of a weight gradient whose input-channel extent is `Cx_total`: channels [c_off, c_off + Cx) of
+// dW [M][Cx_total][KH][KW].  The pixel slabs are those of the WHOLE layer (Cx_total), so a channel's partials and their order do
+// not depend on how the layer's input is split into sources: per-source calls give the bits of one call on the concatenation.
+// Partials are compact ([slab][M][Cx][KH][KW]); slab_reduce_kernel places the rows.
+static int wgrad_launch(const char* name, const float* G, long long g_bs, int M, int Hg, int Wg, const float* X, long long x_bs, int Cx,
+                        int Hx, int Wx, int N, int KH, int KW, int stride, int pt, int pl, float* dW, int Cx_total, int c_off,
+                        int accumulate, float* workspace, void* stream) {
+    DCVIC_CHECK_ARG(G && X && dW && workspace, "%s: null pointer", name);
+    DCVIC_CHECK_ARG(KW >= 1 && KW <= 5 && KH >= 1 && KH <= 5 && stride >= 1 && stride <= 4, "%s: kernel %dx%d stride %d unsupported", name, KH, KW, stride);
+    DCVIC_CHECK_ARG(N > 0 && M > 0 && Cx > 0 && Hg > 0 && Wg > 0 && Hx > 0 && Wx > 0, "%s: empty map N=%d M=%d Cx=%d Hg=%d Wg=%d Hx=%d Wx=%d",
+                    name, N, M, Cx, Hg, Wg, Hx, Wx);
     int slabs = 0;
-    dcvic_conv_wgrad_workspace_floats(N, M, Cx, KH, KW, Hg, &slabs);
+    dcvic_conv_wgrad_workspace_floats(N, M, Cx_total, KH, KW, Hg, &slabs);
     WgradArgs a;
     a.G = G; a.g_bs = g_bs; a.M = M; a.Hg = Hg; a.Wg = Wg;
     a.X = X; a.x_bs = x_bs; a.Cx = Cx; a.Hx = Hx; a.Wx = Wx;
@@ -241,7 +250,7 @@ extern "C" int dcvic_conv_wgrad_f32(const float* G, long long g_bs, int M, int H
     static const bool fuse_env = getenv("DCVIC_WGRAD_FUSED") && getenv("DCVIC_WGRAD_FUSED")[0] == '1';
     const bool rows_fused = KH == 3 && KW == 3 && stride == 1 && fuse_env;
     const long long blocks = (long long)a.mblocks * a.cblocks * (rows_fused ? 1 : KH) * slabs;
-    DCVIC_CHECK_ARG(blocks < (1ll << 31), "conv_wgrad: grid too large");
+    DCVIC_CHECK_ARG(blocks < (1ll << 31), "%s: grid too large", name);
     const int xw = 31 * stride + KW;
     // (stride 4 needs 65 792 .. 66 816 bytes, above 64 KiB: measured to launch on gfx950 without raising the dynamic-LDS limit,
     //  tests/test_gpu_train_kernels.py covers it)
@@ -260,10 +269,27 @@ extern "C" int dcvic_conv_wgrad_f32(const float* G, long long g_bs, int M, int H
         default: conv_wgrad_kernel<5, 1><<<(unsigned)blocks, 256, lds, st>>>(a); break;
     }
     DCVIC_CHECK_LAUNCH("conv_wgrad");
-    const long long len = (long long)M * Cx * KH * KW;
-    slab_reduce_kernel<<<dcvic_cdiv(len, 256), 256, 0, st>>>(workspace, dW, len, slabs, accumulate);
+    const long long taps = (long long)KH * KW, len = (long long)M * Cx * taps;
+    slab_reduce_kernel<<<dcvic_cdiv(len, 256), 256, 0, st>>>(workspace, dW, len, slabs, accumulate, Cx * taps, Cx_total * taps, c_off * taps);
     DCVIC_CHECK_LAUNCH("conv_wgrad_reduce");
     return DCVIC_OK;
+}
+
+extern "C" int dcvic_conv_wgrad_f32(const float* G, long long g_bs, int M, int Hg, int Wg, const float* X, long long x_bs, int Cx, int Hx,
+                                    int Wx, int N, int KH, int KW, int stride, int pt, int pl, float* dW, int accumulate, float* workspace,
+                                    void* stream) {
+    return wgrad_launch("conv_wgrad", G, g_bs, M, Hg, Wg, X, x_bs, Cx, Hx, Wx, N, KH, KW, stride, pt, pl, dW, Cx, 0, accumulate, workspace, stream);
+}
+
+extern "C" int dcvic_conv_wgrad_src_f32(const float* G, long long g_bs, int M, int Hg, int Wg, const float* X, long long x_bs, int Cs, int Hx,
+                                        int Wx, int N, int KH, int KW, int stride, int pt, int pl, float* dW, int Cx_total, int c_off,
+                                        int accumulate, float* workspace, void* stream) {
+    const char* name = "dcvic_conv_wgrad_src_f32";
+    DCVIC_CHECK_ARG(Cs > 0 && Cx_total > 0 && c_off >= 0 && (long long)c_off + Cs <= Cx_total,
+                    "%s: channels [c_off, c_off + Cs) = [%d, %lld) outside Cx_total=%d", name, c_off, (long long)c_off + Cs, Cx_total);
+    DCVIC_CHECK_ARG(Hg <= 0 || Wg <= 0 || M <= 0 || g_bs >= (long long)M * Hg * Wg, "%s: batch stride g_bs=%lld below M*Hg*Wg", name, g_bs);
+    DCVIC_CHECK_ARG(Hx <= 0 || Wx <= 0 || x_bs >= (long long)Cs * Hx * Wx, "%s: batch stride x_bs=%lld below Cs*Hx*Wx", name, x_bs);
+    return wgrad_launch(name, G, g_bs, M, Hg, Wg, X, x_bs, Cs, Hx, Wx, N, KH, KW, stride, pt, pl, dW, Cx_total, c_off, accumulate, workspace, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ per-channel reductions
@@ -288,7 +314,7 @@ extern "C" int dcvic_chan_reduce_f32(const float* a, long long a_bs, const float
 // out[j] (+)= sum_i in[i][j], i ascending (sum over the batch of per-image partials)
 extern "C" int dcvic_sum_rows_f32(const float* in, float* out, int rows, long long len, int accumulate, void* stream) {
     DCVIC_CHECK_ARG(in && out && rows > 0 && len > 0, "sum_rows: bad argument");
-    slab_reduce_kernel<<<dcvic_cdiv(len, 256), 256, 0, (hipStream_t)stream>>>(in, out, len, rows, accumulate);
+    slab_reduce_kernel<<<dcvic_cdiv(len, 256), 256, 0, (hipStream_t)stream>>>(in, out, len, rows, accumulate, len, len, 0);
     DCVIC_CHECK_LAUNCH("sum_rows");
     return DCVIC_OK;
 }

@@ -124,9 +124,10 @@ def _dgrad_plan(mod) -> ops.ConvPlan:
     if isinstance(mod, Linear):
         return ops.ConvPlan(w.t().contiguous(), None, "conv")
     if isinstance(mod, ConvTranspose2d):
-        if mod.kernel_size != 5:
-            raise NotImplementedError("only the k5/s2 transposed convolution is trained")
-        # adjoint of ConvTranspose2d(k5, s2, p2, op1) = Conv2d(k5, s2, p2) with the same [Cin, Cout, k, k] tensor read as [out, in, k, k]
+        # adjoint of ConvTranspose2d(k5, s2, p2, op1) = Conv2d(k5, s2, p2) with the same [Cin, Cout, k, k] tensor read as [out, in, k, k];
+        # of ConvTranspose2d(k3, s1, p1) (the hyper-decoder branches' conv3) = Conv2d(k3, s1, p1) on it
+        if mod.kernel_size == 3:
+            return ops.ConvPlan(w, None, "conv", stride=1, pad=(1, 1))
         return ops.ConvPlan(w, None, "conv", stride=2, pad=(2, 2))
     k, s, p = mod.kernel_size, mod.stride, mod.padding
     if mod.asym_pad:
@@ -147,14 +148,37 @@ def _dgrad_plan(mod) -> ops.ConvPlan:
             for px in (0, 1):
                 ph.append(wt[:, :, list(ks[py])][:, :, :, list(ks[px])].contiguous())
         return ops.ConvPlan.from_phases2(ph)
+    if (k, s, p) == (5, 2, 2):
+        # adjoint (even input sides) = ConvTranspose2d(k5, s2, p2, op1) with the same [Cout, Cin, k, k] tensor read as [in, out, k, k]:
+        # the ELIC encoder's conv1..conv4 and the hyper-encoder's conv2 / conv3
+        return ops.ConvPlan(w, None, "convT")
     raise NotImplementedError(f"conv dgrad for k{k} s{s} p{p}")
 
 
-def conv(ctx: Ctx, x: Var, mod, act: int = ops.ACT_NONE) -> Var:
-    """Conv2d / ConvTranspose2d / Linear stand-ins of dc_vic_amd.layers; bias and (optionally) ReLU / LeakyReLU fused forward."""
-    if act not in (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LRELU02):
-        raise ValueError("only sign-derivable activations may be fused into a differentiable conv")
+_DIFF_ACTS = (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LRELU02, ops.ACT_HALF_TANH)    # derivative from the OUTPUT (ew op 0)
+
+
+def _wgrad_geometry(mod):
+    """(KH, KW, stride, pad, transposed) of the weight gradient of `mod`; transposed: G and X swap roles, result [Cin][Cout][k][k]."""
+    if isinstance(mod, ConvTranspose2d):
+        return (5, 5, 2, 2, True) if mod.kernel_size == 5 else (3, 3, 1, 1, True)
+    if isinstance(mod, Linear):
+        return 1, 1, 1, 0, False
+    return mod.kernel_size, mod.kernel_size, mod.stride, mod.padding, False
+
+
+def _check_s2_input(mod, H: int, W: int) -> None:
+    if isinstance(mod, Conv2d) and (mod.kernel_size, mod.stride, mod.padding) == (5, 2, 2) and (H % 2 or W % 2):
+        raise ValueError(f"differentiable Conv2d(k5, s2, p2) needs even input sides, got {H}x{W}")
+
+
+def conv(ctx: Ctx, x: Var, mod, act: int = ops.ACT_NONE, out: Optional[Tensor] = None) -> Var:
+    """Conv2d / ConvTranspose2d / Linear stand-ins of dc_vic_amd.layers; bias and (optionally) ReLU / LeakyReLU / 0.5 tanh fused forward."""
+    if act not in _DIFF_ACTS:
+        raise ValueError("only activations whose derivative follows from the output (ReLU, LeakyReLU, 0.5 tanh) may be fused into a differentiable conv")
     xd = x.data
+    if x.needs_grad:
+        _check_s2_input(mod, xd.shape[2], xd.shape[3])
     gw = ctx.pgrad(mod.weight)
     trainable = gw is not None
     ups = isinstance(mod, Conv2d) and mod.upsample
@@ -183,7 +207,7 @@ def conv(ctx: Ctx, x: Var, mod, act: int = ops.ACT_NONE) -> Var:
         else:
             plan = mod._get_plan(bf16=False)
     # training ignores the decoder precision: the plans above copy wino / wino44 and never bf16 (layers.allow_bf16 is inference only)
-    y = plan(xin, act=act)
+    y = plan(xin, act=act, out=out)         # (`out`: a destination view, e.g. one half of the hyper-decoder's output)
     out = Var(y)
 
     def back():
@@ -192,7 +216,7 @@ def conv(ctx: Ctx, x: Var, mod, act: int = ops.ACT_NONE) -> Var:
             return
         g = _dense(g)
         if act != ops.ACT_NONE:
-            g = K.ew(0, g, y, act=act)
+            g = K.ew(0, g, _dense(y), act=act)
         if x.needs_grad:
             cached = getattr(mod, "_dgrad", None)
             dp = cached[1] if (not trainable and cached is not None and cached[0] == mod._key()) else None
@@ -206,12 +230,92 @@ def conv(ctx: Ctx, x: Var, mod, act: int = ops.ACT_NONE) -> Var:
             acc(x, dx)
         if trainable:
             xs = _dense(xin)
-            if isinstance(mod, ConvTranspose2d):
-                K.conv_wgrad(xs, g, gw, 5, 5, 2, 2)                 # roles swapped: result is [Cin][Cout][k][k]
-            elif isinstance(mod, Linear):
-                K.conv_wgrad(g, xs, gw, 1, 1, 1, 0)
+            KH, KW, st, pd, swapped = _wgrad_geometry(mod)
+            if swapped:
+                K.conv_wgrad(xs, g, gw, KH, KW, st, pd)             # roles swapped: result is [Cin][Cout][k][k]
             else:
-                K.conv_wgrad(g, xs, gw, mod.kernel_size, mod.kernel_size, mod.stride, mod.padding)
+                K.conv_wgrad(g, xs, gw, KH, KW, st, pd)
+            gb = ctx.pgrad(mod.bias)
+            if gb is not None:
+                K.sum_rows(K.chan_reduce(g), gb, accumulate=True)
+    ctx.tape.append(back)
+    return out
+
+
+# conv_multi's weight gradient: one dcvic_conv_wgrad_src_f32 launch per source (True), or one cat of the sources + one dcvic_conv_wgrad_f32
+# launch (False).  Same bits.  Measured at batch 8 x 256x256 (tools/analysis_tape_bench.py, profiles/analysis_tape_bench.json): 56.99 ms per
+# step per source, 56.79 ms with the cat, the per-source form slower in every alternating round (two or three launch pairs per layer
+# against a few plane copies and one pair), so the cat form is the default.
+WGRAD_PER_SOURCE = False
+
+
+def conv_multi(ctx: Ctx, srcs: Sequence[Var], mod: Conv2d, act: int = ops.ACT_NONE, res: Optional[Var] = None, init: Optional[Var] = None) -> Var:
+    """A Conv2d whose input is the channel concatenation of `srcs` (views welcome: each with its own batch stride), never materialised:
+    act(conv(cat srcs) [+ init] + bias) [+ res].  One data gradient over all input channels, whose channel ranges are added to the
+    sources that need one (a constant source -- the one-hot VQ feature -- takes none), and one weight gradient, written per source into
+    its channel range of the layer's [Cout, Cin, k, k] gradient."""
+    if act not in _DIFF_ACTS:
+        raise ValueError("only activations whose derivative follows from the output (ReLU, LeakyReLU, 0.5 tanh) may be fused into a differentiable conv")
+    if act != ops.ACT_NONE and res is not None:
+        raise ValueError("conv_multi: the residual is added after the activation, whose derivative is then not a function of the output")
+    if not isinstance(mod, Conv2d) or mod.upsample or mod.asym_pad:
+        raise NotImplementedError("conv_multi: plain Conv2d layers only")
+    if not 1 <= len(srcs) <= ops.L.MAX_SRC:
+        raise ValueError(f"conv_multi: 1..{ops.L.MAX_SRC} sources, got {len(srcs)}")
+    chans = [int(v.shape[1]) for v in srcs]
+    if sum(chans) != mod.in_channels:
+        raise ValueError(f"conv_multi: sources hold {chans} channels, the layer reads {mod.in_channels}")
+    if any(v.needs_grad for v in srcs):
+        _check_s2_input(mod, srcs[0].shape[2], srcs[0].shape[3])
+    gw = ctx.pgrad(mod.weight)
+    trainable = gw is not None
+    if trainable:            # the weights move every step: never reuse a cached pack
+        plan = ops.ConvPlan(mod.weight, mod.bias, "conv", stride=mod.stride, pad=(mod.padding, mod.padding))
+    else:
+        plan = mod._get_plan(bf16=False)
+    datas = [v.data for v in srcs]
+    y = plan(datas, act=act, res=res.data if res is not None else None, init=init.data if init is not None else None)
+    out = Var(y)
+
+    def back():
+        g = out.grad
+        if g is None:
+            return
+        g = _dense(g)
+        if res is not None:
+            acc(res, g)
+        if act != ops.ACT_NONE:
+            g = K.ew(0, g, y, act=act)
+        if init is not None:
+            acc(init, g)
+        if any(v.needs_grad for v in srcs):
+            cached = getattr(mod, "_dgrad", None)
+            dp = cached[1] if (not trainable and cached is not None and cached[0] == mod._key()) else None
+            if dp is None:
+                dp = _dgrad_plan(mod)
+                if not trainable:
+                    mod._dgrad = (mod._key(), dp)
+            dx = dp(g)
+            off = 0
+            for v, c in zip(srcs, chans):
+                if v.needs_grad:
+                    acc(v, _dense(dx[:, off:off + c]))
+                off += c
+        if trainable:
+            k, st, pd = mod.kernel_size, mod.stride, mod.padding
+            if WGRAD_PER_SOURCE:
+                off = 0
+                for d, c in zip(datas, chans):
+                    K.conv_wgrad_src(g, d, gw, off, k, k, st, pd)
+                    off += c
+            else:
+                N, _, H, W = datas[0].shape
+                xs = torch.empty((N, sum(chans), H, W), dtype=torch.float32, device=g.device)
+                off = 0
+                for d, c in zip(datas, chans):
+                    ops.copy_planes(xs[:, off:off + c], d, H, W)
+                    off += c
+                K.conv_wgrad(g, xs, gw, k, k, st, pd)
             gb = ctx.pgrad(mod.bias)
             if gb is not None:
                 K.sum_rows(K.chan_reduce(g), gb, accumulate=True)
@@ -487,18 +591,18 @@ def oasis_gan_loss(ctx: Ctx, logits: Var, target: Tensor, is_real: bool, weight:
 
 # ------------------------------------------------------------------------------------------- the rate term (csrc/rate_train.hip)
 def gaussian_rate(ctx: Ctx, y: Var, mu: Var, sigma: Var, noise: Tensor, weights: Optional[Tensor], scale: float, bits: Optional[Tensor],
-                  loss: Optional[Tensor], dy_out: Optional[Tensor] = None) -> Var:
+                  loss: Optional[Tensor], dy_out: Optional[Tensor] = None, lik_out: Optional[Tensor] = None) -> Var:
     """The rate term of one Gaussian-conditional call (GaussianConditional.forward(training=True), ste_gaussian_conditional.py:16-23) in
     one pass: bits[n] += -log2 of image n's noisy likelihoods, loss[0] += sum_n scale * weights[n] * bits[n] (both accumulate: the
     caller zeroes them), and that loss term's gradients are seeded into `y`, `mu` and `sigma` now.  With `dy_out` (a [N, C, H, W] view,
     e.g. a CHARM slice of one 192-channel gradient) the gradient w.r.t. y is written there instead and the caller seeds the parent
-    once.  Returns y_hat = ste_round(y - mu) + mu: a gradient arriving on it goes to `y` unchanged and not to `mu`."""
+    once; `lik_out` (a view too) takes the noisy likelihoods.  Returns y_hat = ste_round(y - mu) + mu: a gradient arriving on it goes to `y` unchanged and not to `mu`."""
     new = lambda: torch.empty(y.shape, dtype=torch.float32, device=y.data.device)
     out = Var(new(), needs_grad=y.needs_grad)
     dy = dy_out if dy_out is not None else (new() if y.needs_grad else None)
     dmu, dsigma = (new() if mu.needs_grad else None), (new() if sigma.needs_grad else None)
-    K.gaussian_rate_train(y.data, mu.data, sigma.data, noise, weights, scale, y_hat=out.data, bits=bits, loss=loss, dy=dy, dmu=dmu,
-                          dsigma=dsigma)
+    K.gaussian_rate_train(y.data, mu.data, sigma.data, noise, weights, scale, y_hat=out.data, lik=lik_out, bits=bits, loss=loss, dy=dy,
+                          dmu=dmu, dsigma=dsigma)
     if dy is not None and dy_out is None:
         acc(y, dy)
     if dmu is not None:
@@ -513,7 +617,8 @@ def gaussian_rate(ctx: Ctx, y: Var, mu: Var, sigma: Var, noise: Tensor, weights:
     return out
 
 
-def eb_rate(ctx: Ctx, z: Var, eb, noise: Tensor, weights: Optional[Tensor], scale: float, bits: Optional[Tensor], loss: Optional[Tensor]) -> Var:
+def eb_rate(ctx: Ctx, z: Var, eb, noise: Tensor, weights: Optional[Tensor], scale: float, bits: Optional[Tensor], loss: Optional[Tensor],
+            lik_out: Optional[Tensor] = None) -> Var:
     """The rate term of the entropy bottleneck `eb` (EntropyBottleneck.forward(training=True)): bits / loss as in gaussian_rate; the
     loss term's gradient is seeded into `z` and, when `eb`'s parameters belong to one of ctx's groups, added to their views of the flat
     gradient buffer.  Returns z_hat = ste_round(z - medians) + medians: its gradient goes to `z` unchanged, none to the medians."""
@@ -522,8 +627,8 @@ def eb_rate(ctx: Ctx, z: Var, eb, noise: Tensor, weights: Optional[Tensor], scal
     grads = [ctx.pgrad(getattr(eb, name)) for name in K.EB_PARAM_NAMES]
     grads = None if any(g is None for g in grads) else grads
     dz = torch.empty_like(zd) if z.needs_grad else None
-    K.eb_rate_train(zd, _dense(noise), eb.raw_params(), eb.quantiles.data[:, 0, 1], weights, scale, z_hat=out.data, bits=bits, loss=loss, dz=dz,
-                    grads=grads)
+    K.eb_rate_train(zd, _dense(noise), eb.raw_params(), eb.quantiles.data[:, 0, 1], weights, scale, z_hat=out.data, lik=lik_out, bits=bits, loss=loss,
+                    dz=dz, grads=grads)
     if dz is not None:
         acc(z, dz)
 

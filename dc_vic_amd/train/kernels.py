@@ -37,6 +37,21 @@ def conv_wgrad(G: Tensor, X: Tensor, dW: Tensor, KH: int, KW: int, stride: int, 
                                      1 if accumulate else 0, _p(ws), _stream()), "conv_wgrad")
 
 
+def conv_wgrad_src(G: Tensor, X: Tensor, dW: Tensor, c_off: int, KH: int, KW: int, stride: int, pad: int, accumulate: bool = True) -> None:
+    """The weight gradient of ONE source X [N, Cs, Hx, Wx] (a channel-slice view with its own batch stride) of a multi-source
+    convolution: dW[:, c_off:c_off + Cs] (+)= ..., dW contiguous [M, Cx_total, KH, KW].  One call per source gives the bits of
+    conv_wgrad on the concatenated input (dcvic_conv_wgrad_src_f32)."""
+    N, M, Hg, Wg = _chk4(G, "wgrad_src G")
+    Nx, Cs, Hx, Wx = _chk4(X, "wgrad_src X")
+    if N != Nx or dW.dim() != 4 or not dW.is_contiguous() or dW.dtype != torch.float32 or tuple(dW.shape[2:]) != (KH, KW) or dW.shape[0] != M:
+        raise ValueError(f"conv_wgrad_src: shapes G{tuple(G.shape)} X{tuple(X.shape)} dW{tuple(dW.shape)}")
+    Ct = int(dW.shape[1])
+    need = int(lib().dcvic_conv_wgrad_workspace_floats(N, M, Ct, KH, KW, Hg, None))
+    ws = _workspace(need, G.device, "wgrad")
+    check(lib().dcvic_conv_wgrad_src_f32(_p(G), _bs(G), M, Hg, Wg, _p(X), _bs(X), Cs, Hx, Wx, N, KH, KW, stride, pad, pad, _p(dW), Ct, int(c_off),
+                                         1 if accumulate else 0, _p(ws), _stream()), "conv_wgrad_src")
+
+
 def chan_reduce(a: Tensor, b: Optional[Tensor] = None) -> Tensor:
     """[N, C, H, W] -> [N, C]: sum_p a (* b)."""
     N, Cc, H, W = _chk4(a, "chan_reduce a")

@@ -4,11 +4,16 @@ discriminator.  Reference: hyperprior_dc_vic_model.py:208-274 (forward, is_train
 elic_dual_beta_ft_autoencoder.py:332-359, swin_vq_estimator.py:70-98, vq_fusion_module.py:78-126 driving ldm
 model.py:462-568, dual_beta_taming_nlayer_discriminator.py:16-89 / taming_nlayer_discriminator.py:29-119.
 Only decoder, vq_estimator and fusion_module are trainable (dual_cond_gan_distortion_vq_code_trainer.py:47-52); the frozen
-VQGAN decoder is differentiated through (data gradients only)."""
+VQGAN decoder is differentiated through (data gradients only).
+
+The analysis side (stages 1-1 / 1-2: encoder, hyper-encoder, entropy bottleneck, hyper-decoder, CHARM) follows further down:
+elic_dual_beta_ft_autoencoder.py:108-141, minnen20_hyperprior.py:20-55, minnen20_charm_context_model.py:70-119 (is_train=True,
+calc_q_likelihood=True) and hyperprior_charm_dc_vic_model.py:24-56.  Nothing there reads a cached pack, a stacked hyper-partial plan,
+a cached beta vector or a CDF table: every plan is built from the live weights of the step."""
 from __future__ import annotations
 
 import math
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -88,6 +93,178 @@ def decoder_get_feats(ctx: Ctx, dec, y_hat: Tensor, beta_1, beta_2):
         if len(feats) == len(query):
             break
     return feat_1, feats
+
+
+# ------------------------------------------------------------------------------------------- analysis side
+def encoder_forward(ctx: Ctx, enc, x: Tensor, feat: Tensor, beta_1, beta_2) -> Var:
+    """ElicDualBetaFtVqScEncoder.forward with a tape: the image and the VQ feature (latent | one-hot indices) are constants, the
+    beta vectors are per sample ([B] tensors) or shared (scalars); beta-FT follows each layer."""
+    cond = cond_vector(ctx, enc, beta_1, beta_2, x.device)
+
+    def ft(i: int, v: Var) -> Var:
+        s, t = beta_vectors(ctx, enc.beta_ft_list[i], cond)
+        return A.chan_affine(ctx, v, s, t)
+    h = ft(0, A.conv(ctx, A.const(x), enc.conv1))
+    h = ft(1, bottleneck_blocks(ctx, enc.block1, h))
+    h = ft(2, A.conv(ctx, h, enc.conv2))
+    h = ft(3, bottleneck_blocks(ctx, enc.block2, h))
+    h = ft(4, nlam(ctx, enc.attn2, h))
+    h = ft(5, A.conv(ctx, h, enc.conv3))
+    h = A.conv_multi(ctx, [A.const(feat), h], enc.projection, res=h)          # x + conv3x3(cat[feat, x])   (:131-132)
+    h = ft(6, bottleneck_blocks(ctx, enc.block3, h))
+    h = ft(7, A.conv(ctx, h, enc.conv4))
+    return ft(8, nlam(ctx, enc.attn4, h))
+
+
+def hyper_encoder_forward(ctx: Ctx, he, y: Var) -> Var:
+    h = A.conv(ctx, y, he.conv1, act=ops.ACT_RELU)
+    h = A.conv(ctx, h, he.conv2, act=ops.ACT_RELU)
+    return A.conv(ctx, h, he.conv3)
+
+
+def hyper_decoder_forward(ctx: Ctx, hd, z_hat: Var) -> Var:
+    """Minnen20HyperDecoder.forward: the two branches write the halves of ONE hyper_out; its gradient is handed to them as views."""
+    N, _, H, W = z_hat.shape
+    half = hd.half
+    buf = torch.empty((N, 2 * half, 4 * H, 4 * W), dtype=torch.float32, device=z_hat.data.device)
+    outs = []
+    for blk, dst in ((hd.hd_mu, buf[:, :half]), (hd.hd_std, buf[:, half:])):
+        h = A.conv(ctx, z_hat, blk.conv1, act=ops.ACT_RELU)
+        h = A.conv(ctx, h, blk.conv2, act=ops.ACT_RELU)
+        outs.append(A.conv(ctx, h, blk.conv3, out=dst))
+    hyper_out = Var(buf)
+
+    def back():
+        if hyper_out.grad is not None:
+            A.acc(outs[0], hyper_out.grad[:, :half])
+            A.acc(outs[1], hyper_out.grad[:, half:])
+    ctx.tape.append(back)
+    return hyper_out
+
+
+def _slice_transform(ctx: Ctx, st, srcs, act: int = ops.ACT_NONE) -> Var:
+    h = A.conv_multi(ctx, srcs, st.model[0], act=ops.ACT_RELU)
+    h = A.conv(ctx, h, st.model[2], act=ops.ACT_RELU)
+    return A.conv(ctx, h, st.model[4], act=act)
+
+
+def charm_forward_train(ctx: Ctx, cm, y: Var, hyper_out: Var, entropy_model_y, noise: Tensor, weights: Optional[Tensor], scale: float,
+                        bits: Tensor, loss: Tensor, q_bits: Optional[Tensor] = None) -> Dict:
+    """Minnen20CharmContextModel.forward(is_train=True, calc_q_likelihood=True) with a tape.  Per slice: mu and sigma from
+    [hyper | y_hat[:k]] (multi-source convs on views, no cat), the gaussian_rate tape op on the slice views (STE output, noisy
+    likelihood, bits / loss accumulated, rate gradients seeded now), the no-grad quantised likelihood from the eval kernel, the LRP
+    with 0.5 tanh on [hyper_mean | support | yq], y_hat_i = yq + lrp into ONE y_hat buffer whose leading channels are the next
+    slices' support.  A gradient arriving on the returned y_hat reaches `y` through the STE and earlier slices through the supports.
+    -> dict(y_hat: Var, likelihood, q_likelihood, symbols (int32, of the quantised pass))."""
+    N, Cy, H, W = y.shape
+    dev = y.data.device
+    sc, ns, hm = cm.slice_ch, cm.num_slices, cm.hyper_half
+    if Cy != sc * ns or tuple(hyper_out.shape) != (N, 2 * hm, H, W) or tuple(noise.shape) != tuple(y.shape):
+        raise ValueError(f"charm_forward_train: y {tuple(y.shape)}, hyper_out {tuple(hyper_out.shape)}, noise {tuple(noise.shape)}")
+    new = lambda dtype=torch.float32: torch.empty((N, Cy, H, W), dtype=dtype, device=dev)
+    y_hat_buf, dy_rate, lik, q_lik, sym = new(), new(), new(), new(), new(torch.int32)
+    table = entropy_model_y._table_dev(y.data)
+    h_mean, h_scale = Var(hyper_out.data[:, :hm], hyper_out.needs_grad), Var(hyper_out.data[:, hm:], hyper_out.needs_grad)
+    y_sl = [Var(y.data[:, i * sc:(i + 1) * sc], y.needs_grad) for i in range(ns)]
+    yh_sl = []
+
+    def back_inputs():                                   # appended first: runs after every slice's backward
+        if hyper_out.needs_grad and (h_mean.grad is not None or h_scale.grad is not None):
+            dh = torch.zeros(hyper_out.shape, dtype=torch.float32, device=dev)
+            if h_mean.grad is not None:
+                ops.copy_planes(dh[:, :hm], h_mean.grad, H, W)
+            if h_scale.grad is not None:
+                ops.copy_planes(dh[:, hm:], h_scale.grad, H, W)
+            A.acc(hyper_out, dh)
+        if y.needs_grad:
+            ste = torch.zeros(y.shape, dtype=torch.float32, device=dev)
+            for i, v in enumerate(y_sl):
+                if v.grad is not None:
+                    ops.copy_planes(ste[:, i * sc:(i + 1) * sc], v.grad, H, W)
+            A.acc(y, A.K.ew(10, None, dy_rate, ste))          # rate gradient (seeded at forward time) + what came through the STE
+    ctx.tape.append(back_inputs)
+
+    for i in range(ns):
+        sl = slice(i * sc, (i + 1) * sc)
+        k = cm._n_support(i)
+        sup = Var(y_hat_buf[:, :k * sc]) if k > 0 else None
+        if sup is not None:
+            def back_support(sup=sup, k=k):              # after this slice's three transforms: hand the support's gradient to its slices
+                if sup.grad is not None:
+                    for j in range(k):
+                        A.acc(yh_sl[j], A._dense(sup.grad[:, j * sc:(j + 1) * sc]))
+            ctx.tape.append(back_support)
+        support = [sup] if sup is not None else []
+        mu = _slice_transform(ctx, cm.mean_slice_transforms[i], [h_mean] + support)
+        sigma = _slice_transform(ctx, cm.scale_slice_transforms[i], [h_scale] + support)
+        yq = A.gaussian_rate(ctx, y_sl[i], mu, sigma, noise[:, sl], weights, scale, bits, loss, dy_out=dy_rate[:, sl] if y.needs_grad else None,
+                             lik_out=lik[:, sl])
+        # the quantised likelihood (no gradient): the eval kernel on the same mu / sigma
+        ops.gaussian_rate(y_sl[i].data, None, mu.data, sigma.data, table, None, sym[:, sl], None, q_lik[:, sl], q_bits)
+        lrp = _slice_transform(ctx, cm.lrp_slice_transforms[i], [h_mean] + support + [yq], act=ops.ACT_HALF_TANH)
+        ops.add(yq.data, lrp.data, out=y_hat_buf[:, sl])
+        yh = Var(y_hat_buf[:, sl])
+        yh_sl.append(yh)
+
+        def back_add(yh=yh, yq=yq, lrp=lrp):
+            if yh.grad is not None:
+                A.acc(yq, yh.grad)
+                A.acc(lrp, yh.grad)
+        ctx.tape.append(back_add)
+    y_hat = Var(y_hat_buf)
+
+    def back_out():                                      # appended last: runs first
+        if y_hat.grad is not None:
+            for i in range(ns):
+                A.acc(yh_sl[i], A._dense(y_hat.grad[:, i * sc:(i + 1) * sc]))
+    ctx.tape.append(back_out)
+    return dict(y_hat=y_hat, likelihood=lik, q_likelihood=q_lik, symbols=sym)
+
+
+def estimate_entropy_train(ctx: Ctx, model, y: Var, noise_y: Tensor, noise_z: Tensor, weights: Optional[Tensor] = None, scale: float = 1.0) -> Dict:
+    """HyperpriorCharmDualCondVicModel.estimate_entropy(is_train=True) with a tape: the reference's keys (quantized_code.y / .z are
+    Vars: the decoder side continues the tape from them), the per-image bits of the noisy and of the quantised likelihoods, and
+    `loss` [1] = sum_n scale * weights[n] * (bits_y[n] + bits_z[n]), whose gradients are already seeded."""
+    from ..entropy import pack_entropy_bottleneck
+    N = y.shape[0]
+    dev = y.data.device
+    z = hyper_encoder_forward(ctx, model.hyperencoder, y)
+    bits_y, bits_z, q_bits_y, q_bits_z = (torch.zeros(N, dtype=torch.float32, device=dev) for _ in range(4))
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    eb = model.entropy_model_z
+    z_lik, z_qlik = torch.empty_like(z.data), torch.empty_like(z.data)
+    z_sym = torch.empty(z.shape, dtype=torch.int32, device=dev)
+    z_hat = A.eb_rate(ctx, z, eb, noise_z, weights, scale, bits_z, loss, lik_out=z_lik)
+    # the quantised likelihood of z (no gradient): the eval kernel on packs made from the LIVE parameters, not eb.packs()
+    packs = pack_entropy_bottleneck({f"eb.{k}": v.data for k, v in eb.named_parameters()}, "eb")
+    ops.eb_rate(A._dense(z.data), packs, torch.empty_like(z.data), z_sym, z_qlik, q_bits_z)
+    hyper_out = hyper_decoder_forward(ctx, model.hyperdecoder, z_hat)
+    r = charm_forward_train(ctx, model.context_model, y, hyper_out, model.entropy_model_y, noise_y, weights, scale, bits_y, loss, q_bits=q_bits_y)
+    return {"quantized_code": {"y": r["y_hat"], "z": z_hat}, "latent_code": {"y": y, "z": z},
+            "likelihoods": {"y": r["likelihood"], "z": z_lik}, "q_likelihoods": {"y": r["q_likelihood"], "z": z_qlik},
+            "bits_y": bits_y, "bits_z": bits_z, "q_bits_y": q_bits_y, "q_bits_z": q_bits_z, "loss": loss,
+            "symbols": {"y": r["symbols"], "z": z_sym}, "hyper_out": hyper_out}
+
+
+def analysis_forward(ctx: Ctx, model, x: Tensor, beta_rate, beta_vq, vq_indices: Optional[Tensor] = None, noise_y: Optional[Tensor] = None,
+                     noise_z: Optional[Tensor] = None, generator: Optional[torch.Generator] = None, weights: Optional[Tensor] = None,
+                     scale: float = 1.0) -> Dict:
+    """The analysis side of one training step on a preprocessed batch x [N, 3, H, W] (sides multiples of 64): the no-grad VQ encode,
+    the beta-conditioned encoder and estimate_entropy_train.  Without explicit noise, U(-0.5, 0.5) is drawn on the device from
+    `generator` (as entropy._train_noise does).  -> estimate_entropy_train's dict plus gt_vq_latent / gt_vq_indices."""
+    from ..entropy import _train_noise
+    if x.shape[2] % 64 or x.shape[3] % 64:
+        raise ValueError(f"analysis_forward: image sides must be multiples of 64, got {tuple(x.shape[2:])}")
+    with torch.no_grad():
+        zq, idx, feat = model.vq_encode(x, vq_indices, want_feat=True)
+    y = encoder_forward(ctx, model.encoder, x, feat, beta_rate, beta_vq)
+    N, Cy, H, W = y.shape
+    like_z = torch.empty((N, model.hyperencoder.conv3.out_channels, H // 4, W // 4), dtype=torch.float32, device=x.device)
+    noise_y = _train_noise(y.data, noise_y, generator)
+    noise_z = _train_noise(like_z, noise_z, generator)
+    out = estimate_entropy_train(ctx, model, y, noise_y, noise_z, weights, scale)
+    out.update(gt_vq_latent=zq, gt_vq_indices=idx)
+    return out
 
 
 # ------------------------------------------------------------------------------------------- Swin estimator

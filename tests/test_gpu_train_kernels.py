@@ -10,36 +10,22 @@ claim determinism are rerun and compared bit for bit.
 
 Set DCVIC_TEST_RATIOS=<file> to have the worst error / bound of each kernel family written there as JSON."""
 import ctypes as C
-import json
 import math
-import os
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+from kernel_bounds import DEV, U, TINY, cpu64, rnd, urnd, view_on_device, within, ratios_mark, write_ratios  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-U = 2.0 ** -24                    # unit roundoff of fp32
-TINY = 2.0 ** -126                # absolute floor: results below the smallest normal may be flushed
-RATIOS = {}
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _report_ratios():
+    mark = ratios_mark()
     yield
-    path = os.environ.get("DCVIC_TEST_RATIOS")
-    if path:
-        with open(path, "w") as f:
-            json.dump(dict(sorted(RATIOS.items())), f, indent=1)
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    return torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale
-
-
-def urnd(*shape, seed=0, lo=0.0, hi=1.0):
-    return torch.rand(shape, generator=torch.Generator().manual_seed(seed)) * (hi - lo) + lo
+    write_ratios(since=mark)
 
 
 def K():
@@ -50,39 +36,6 @@ def K():
 def L():
     from dc_vic_amd._lib import lib
     return lib()
-
-
-def cpu64(t):
-    return t.detach().cpu().double()
-
-
-def within(family, got, ref, bound, what=""):
-    """|got - ref| <= bound + TINY element by element; records the worst ratio of the family."""
-    got = cpu64(got)
-    ref = ref.double()
-    bound = torch.as_tensor(bound, dtype=torch.float64).expand_as(ref)
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert torch.isfinite(got).all(), f"{family} {what}: non-finite output"
-    ratio = (got - ref).abs() / (bound + TINY)
-    worst = float(ratio.max()) if ratio.numel() else 0.0
-    RATIOS[family] = max(RATIOS.get(family, 0.0), worst)
-    if worst > 1.0:
-        i = int(ratio.flatten().argmax())
-        idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), ref.shape))
-        raise AssertionError(f"{family} {what}: error / bound = {worst:.3g} at {idx}: got {got.flatten()[i].item()!r} "
-                             f"ref {ref.flatten()[i].item()!r} bound {bound.flatten()[i].item():.3g}")
-    return worst
-
-
-def view_on_device(t, extra=0, offset=0):
-    """A device copy of the contiguous [N, C, H, W] tensor t with batch stride C*H*W + extra and storage offset `offset` (floats):
-    a channel-slice-like view (batch stride != C*H*W); an odd offset makes the base pointer misaligned for 16-byte loads."""
-    N, Cc, H, W = t.shape
-    bs = Cc * H * W + extra
-    buf = torch.full((offset + N * bs,), float("nan"), dtype=torch.float32, device=DEV)
-    v = buf.as_strided((N, Cc, H, W), (bs, H * W, W, 1), offset)
-    v.copy_(t)
-    return v
 
 
 def wgrad_slabs(N, M, Cx, KH, KW, Hg):

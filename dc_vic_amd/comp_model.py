@@ -612,7 +612,7 @@ class HyperpriorDualCondVicModel(HyperpriorVicModel):
             out = self.run_model(x, is_train=False, beta_rate=beta_rate, beta_vq=beta_vq)
             ms, psnr = metrics.ms_ssim_psnr(out["real_images"], out["fake_images"])
             emb, gt = out["out_vq_latent"], out["gt_vq_latent"].contiguous()
-            vq_mse = K.reduce_loss(0, emb, gt, 1.0 / emb.numel())
+            vq_mse = K.reduce_loss(K.SUM_SQ_ERR, emb, gt, 1.0 / emb.numel())
             rows.append(dict(idx=idx + 1, bpp=float(out["bpp"]), psnr=float(psnr[0]), ms_ssim=float(ms[0]), vq_acc=float(out["vq_accuracy"]),
                              vq_mse=float(vq_mse[0])))
         return rows

@@ -74,6 +74,16 @@ def invalidate_weight_caches(module: nn.Module) -> None:
             m._graphs.clear()
 
 
+def copy_kernel_flags(plan, layer, wino: bool = True, bf16: bool = False):
+    """The kernel families `layer` opted into (allow_winograd, allow_bf16), copied to a plan made from its weights -- the one place that
+    does it.  `wino=False`: the plan is not a Conv2d(k3, s1, p1); `bf16` is passed by inference only.  (F(4x4) counts only where F(2x2)
+    does: ConvPlan never looks at wino44 without wino.)"""
+    plan.wino = wino and bool(getattr(layer, "wino", False))
+    plan.wino44 = plan.wino and bool(getattr(layer, "wino44", False))
+    plan.bf16 = bf16 and bool(getattr(layer, "bf16", False)) and not getattr(layer, "bf16_keep_fp32", False)
+    return plan
+
+
 class _Packed(nn.Module):
     def __init__(self):
         super().__init__()
@@ -89,10 +99,7 @@ class _Packed(nn.Module):
         if self._plan is None or self._plan_key != k:
             self._plan = self._build_plan()
             self._plan_key = k
-        self._plan.wino = bool(getattr(self, "wino", False))
-        self._plan.wino44 = bool(getattr(self, "wino44", False))
-        self._plan.bf16 = bf16 and bool(getattr(self, "bf16", False)) and not getattr(self, "bf16_keep_fp32", False)
-        return self._plan
+        return copy_kernel_flags(self._plan, self, bf16=bf16)
 
     def _build_plan(self):
         raise NotImplementedError

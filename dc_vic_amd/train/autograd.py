@@ -9,13 +9,13 @@ the data-parallel all-reduce each see ONE contiguous tensor.  No torch autograd,
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence, Union
 
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..layers import Conv2d, ConvTranspose2d, GroupNorm, LayerNormC, Linear, invalidate_weight_caches
+from ..layers import Conv2d, ConvTranspose2d, GroupNorm, LayerNormC, Linear, copy_kernel_flags, invalidate_weight_caches
 from . import kernels as K
 
 Tensor = torch.Tensor
@@ -98,6 +98,20 @@ class Ctx:
                 return v
         return None
 
+    def record(self, entry: Callable[[], None]) -> None:
+        """Append one tape entry: backward() runs the entries last-in first-out, so this one runs after every entry recorded later."""
+        self.tape.append(entry)
+
+    def op(self, data: Tensor, backward: Callable[[Tensor], None], needs_grad: bool = True) -> Var:
+        """The frame of a tape op: the output Var over `data`, and one entry that calls backward(out.grad) if a gradient arrived."""
+        out = Var(data, needs_grad)
+
+        def entry():
+            if out.grad is not None:
+                backward(out.grad)
+        self.record(entry)
+        return out
+
     def backward(self) -> None:
         for fn in reversed(self.tape):
             fn()
@@ -111,11 +125,64 @@ def acc(v: Var, g: Tensor) -> None:
     if v.grad is None:
         v.grad = g
     else:
-        v.grad = K.ew(10, None, v.grad.contiguous(), g.contiguous())
+        v.grad = K.ew(K.EW_ADD, None, v.grad.contiguous(), g.contiguous())
 
 
 def _dense(t: Tensor) -> Tensor:
     return t if t.is_contiguous() else ops.copy_planes(torch.empty(t.shape, dtype=torch.float32, device=t.device), t, t.shape[2], t.shape[3])
+
+
+# ------------------------------------------------------------------------------------------- channel views
+def _cat(datas: Sequence[Tensor]) -> Tensor:
+    N, _, H, W = datas[0].shape
+    buf = torch.empty((N, sum(d.shape[1] for d in datas), H, W), dtype=torch.float32, device=datas[0].device)
+    off = 0
+    for d in datas:
+        ops.copy_planes(buf[:, off:off + d.shape[1]], d, H, W)
+        off += d.shape[1]
+    return buf
+
+
+def _hand_out(g: Tensor, parts: Sequence[Var]) -> None:
+    """Consecutive channel ranges of `g`, as dense copies, to the parts that take a gradient."""
+    off = 0
+    for p in parts:
+        c = p.shape[1]
+        if p.needs_grad:
+            acc(p, _dense(g[:, off:off + c]))
+        off += c
+
+
+def split_channels(ctx: Ctx, parent: Var, sizes: Sequence[int]) -> List[Var]:
+    """Vars over consecutive channel-slice views of `parent`.  The entry recorded HERE runs after every consumer of the views: it
+    gathers the gradients that arrived (zeros where none did) into one buffer of the parent's shape and adds it to the parent's."""
+    if sum(sizes) != parent.shape[1]:
+        raise ValueError(f"split_channels: sizes {tuple(sizes)} of {parent.shape[1]} channels")
+    offs = [sum(sizes[:i]) for i in range(len(sizes))]
+    views = [Var(parent.data[:, o:o + c], parent.needs_grad) for o, c in zip(offs, sizes)]
+
+    def gather():
+        if all(v.grad is None for v in views):
+            return
+        buf = torch.zeros(parent.shape, dtype=torch.float32, device=parent.data.device)
+        for v, o, c in zip(views, offs, sizes):
+            if v.grad is not None:
+                ops.copy_planes(buf[:, o:o + c], v.grad, parent.shape[2], parent.shape[3])
+        acc(parent, buf)
+    ctx.record(gather)
+    return views
+
+
+def join_channels(ctx: Ctx, buf: Tensor, parts: Sequence[Var]) -> Var:
+    """A Var over `buf`, whose consecutive channel slices ARE the parts' data (written there through `out=`): its gradient is handed
+    to the parts slice by slice."""
+    if sum(p.shape[1] for p in parts) != buf.shape[1]:
+        raise ValueError(f"join_channels: parts of {[p.shape[1] for p in parts]} channels in a buffer of {buf.shape[1]}")
+    return ctx.op(buf, lambda g: _hand_out(g, parts))
+
+
+def cat_channels(ctx: Ctx, parts: Sequence[Var]) -> Var:
+    return join_channels(ctx, _cat([p.data for p in parts]), parts)
 
 
 # ------------------------------------------------------------------------------------------- convolution family
@@ -134,10 +201,8 @@ def _dgrad_plan(mod) -> ops.ConvPlan:
         raise NotImplementedError("the ldm Downsample conv is encoder-side only (never differentiated)")
     if s == 1:
         plan = ops.ConvPlan(w.flip(2, 3).transpose(0, 1).contiguous(), None, "conv", pad=(k - 1 - p, k - 1 - p))
-        # the data gradient of a Conv2d(k3, s1, p1) is again one: Winograd wherever the forward layer opted in (layers.allow_winograd)
-        plan.wino = bool(getattr(mod, "wino", False)) and (k, p) == (3, 1)
-        plan.wino44 = plan.wino and bool(getattr(mod, "wino44", False))   # (F(4x4) where the forward layer may use it: decoder + fusion)
-        return plan
+        # the data gradient of a Conv2d(k3, s1, p1) is again one: Winograd (F(4x4) too) wherever the forward layer opted in (layers.allow_winograd)
+        return copy_kernel_flags(plan, mod, wino=(k, p) == (3, 1))
     if (k, s, p) == (4, 2, 1):
         # adjoint = ConvTranspose2d(k4, s2, p1): output row 2m+py takes (input row, ky) in {(m-1, 3), (m, 1)} for py = 0 and
         # {(m, 2), (m+1, 0)} for py = 1 (oy = 2 iy - 1 + ky); four 2x2 sub-pixel convolutions
@@ -155,7 +220,7 @@ def _dgrad_plan(mod) -> ops.ConvPlan:
     raise NotImplementedError(f"conv dgrad for k{k} s{s} p{p}")
 
 
-_DIFF_ACTS = (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LRELU02, ops.ACT_HALF_TANH)    # derivative from the OUTPUT (ew op 0)
+_DIFF_ACTS = (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LRELU02, ops.ACT_HALF_TANH)    # derivative from the OUTPUT (K.EW_ACT_GRAD)
 
 
 def _wgrad_geometry(mod):
@@ -172,254 +237,170 @@ def _check_s2_input(mod, H: int, W: int) -> None:
         raise ValueError(f"differentiable Conv2d(k5, s2, p2) needs even input sides, got {H}x{W}")
 
 
-def conv(ctx: Ctx, x: Var, mod, act: int = ops.ACT_NONE, out: Optional[Tensor] = None) -> Var:
-    """Conv2d / ConvTranspose2d / Linear stand-ins of dc_vic_amd.layers; bias and (optionally) ReLU / LeakyReLU / 0.5 tanh fused forward."""
-    if act not in _DIFF_ACTS:
-        raise ValueError("only activations whose derivative follows from the output (ReLU, LeakyReLU, 0.5 tanh) may be fused into a differentiable conv")
-    xd = x.data
-    if x.needs_grad:
-        _check_s2_input(mod, xd.shape[2], xd.shape[3])
-    gw = ctx.pgrad(mod.weight)
-    trainable = gw is not None
-    ups = isinstance(mod, Conv2d) and mod.upsample
-    if ups:
-        # differentiable path: explicit nearest x2 then the plain 3x3 convolution (ldm model.py:53-57)
-        xin = K.resample2(_dense(xd), down=False)
-        cached = None if trainable else getattr(mod, "_plain_plan", None)
-        plan = cached[1] if cached is not None and cached[0] == mod._key() else None
-        if plan is None:
-            plan = ops.ConvPlan(mod.weight, mod.bias, "conv", pad=(1, 1))
-            plan.wino = bool(getattr(mod, "wino", False))
-            plan.wino44 = plan.wino and bool(getattr(mod, "wino44", False))
-            if not trainable:
-                mod._plain_plan = (mod._key(), plan)   # frozen weights (the VQGAN decoder's Upsample convs): pack once per weight version
-    else:
-        xin = xd
-        if trainable:        # the weights move every step: never reuse a cached pack
-            if isinstance(mod, ConvTranspose2d):
-                plan = ops.ConvPlan(mod.weight, mod.bias, "convT")
-            elif isinstance(mod, Linear):
-                plan = ops.ConvPlan(mod.weight, mod.bias, "conv")
-            else:
-                plan = ops.ConvPlan(mod.weight, mod.bias, "conv", stride=mod.stride, pad=(mod.padding, mod.padding))
-                plan.wino = bool(getattr(mod, "wino", False))    # (the SFT fusion blocks train; their 3x3 convs stay on Winograd)
-                plan.wino44 = plan.wino and bool(getattr(mod, "wino44", False))
-        else:
-            plan = mod._get_plan(bf16=False)
-    # training ignores the decoder precision: the plans above copy wino / wino44 and never bf16 (layers.allow_bf16 is inference only)
-    y = plan(xin, act=act, out=out)         # (`out`: a destination view, e.g. one half of the hyper-decoder's output)
-    out = Var(y)
-
-    def back():
-        g = out.grad
-        if g is None:
-            return
-        g = _dense(g)
-        if act != ops.ACT_NONE:
-            g = K.ew(0, g, _dense(y), act=act)
-        if x.needs_grad:
-            cached = getattr(mod, "_dgrad", None)
-            dp = cached[1] if (not trainable and cached is not None and cached[0] == mod._key()) else None
-            if dp is None:
-                dp = _dgrad_plan(mod)
-                if not trainable:
-                    mod._dgrad = (mod._key(), dp)          # keyed by the weights' version: a reloaded checkpoint rebuilds it
-            dx = dp(g)
-            if ups:
-                dx = K.resample2(dx, down=True)
-            acc(x, dx)
-        if trainable:
-            xs = _dense(xin)
-            KH, KW, st, pd, swapped = _wgrad_geometry(mod)
-            if swapped:
-                K.conv_wgrad(xs, g, gw, KH, KW, st, pd)             # roles swapped: result is [Cin][Cout][k][k]
-            else:
-                K.conv_wgrad(g, xs, gw, KH, KW, st, pd)
-            gb = ctx.pgrad(mod.bias)
-            if gb is not None:
-                K.sum_rows(K.chan_reduce(g), gb, accumulate=True)
-    ctx.tape.append(back)
-    return out
-
-
-# conv_multi's weight gradient: one dcvic_conv_wgrad_src_f32 launch per source (True), or one cat of the sources + one dcvic_conv_wgrad_f32
-# launch (False).  Same bits.  Measured at batch 8 x 256x256 (tools/analysis_tape_bench.py, profiles/analysis_tape_bench.json): 56.99 ms per
-# step per source, 56.79 ms with the cat, the per-source form slower in every alternating round (two or three launch pairs per layer
-# against a few plane copies and one pair), so the cat form is the default.
+# The weight gradient of a convolution of several sources: one dcvic_conv_wgrad_src_f32 launch per source (True), or one cat of the
+# sources + one dcvic_conv_wgrad_f32 launch (False).  Same bits.  Measured at batch 8 x 256x256 (tools/analysis_tape_bench.py,
+# profiles/analysis_tape_bench.json): 56.99 ms per step per source, 56.79 ms with the cat, the per-source form slower in every alternating
+# round (two or three launch pairs per layer against a few plane copies and one pair), so the cat form is the default.
 WGRAD_PER_SOURCE = False
 
 
-def conv_multi(ctx: Ctx, srcs: Sequence[Var], mod: Conv2d, act: int = ops.ACT_NONE, res: Optional[Var] = None, init: Optional[Var] = None) -> Var:
-    """A Conv2d whose input is the channel concatenation of `srcs` (views welcome: each with its own batch stride), never materialised:
-    act(conv(cat srcs) [+ init] + bias) [+ res].  One data gradient over all input channels, whose channel ranges are added to the
-    sources that need one (a constant source -- the one-hot VQ feature -- takes none), and one weight gradient, written per source into
-    its channel range of the layer's [Cout, Cin, k, k] gradient."""
+def _cached(mod, attr: str, trainable: bool, build):
+    """build(), kept on a frozen layer as `attr` = (mod._key(), value): keyed by the weights' version, so a reloaded checkpoint rebuilds
+    it.  Trainable weights move every step: nothing is read from or left in the cache."""
+    if trainable:
+        return build()
+    cached = getattr(mod, attr, None)
+    if cached is None or cached[0] != mod._key():
+        cached = (mod._key(), build())
+        setattr(mod, attr, cached)
+    return cached[1]
+
+
+def _forward_plan(mod, trainable: bool, ups: bool) -> ops.ConvPlan:
+    """The fp32 plan of `mod` on the tape.  Training ignores the decoder precision: wino / wino44 are copied, never the bf16 flag
+    (layers.allow_bf16 is inference only)."""
+    if ups:      # the differentiable Upsample conv is an explicit nearest x2, then this plain 3x3 convolution (ldm model.py:53-57)
+        return _cached(mod, "_plain_plan", trainable, lambda: copy_kernel_flags(ops.ConvPlan(mod.weight, mod.bias, "conv", pad=(1, 1)), mod))
+    if trainable:                        # built from the live weights (the SFT fusion blocks train; their 3x3 convs stay on Winograd)
+        return copy_kernel_flags(mod._build_plan(), mod)
+    return mod._get_plan(bf16=False)
+
+
+def _param_grads(ctx: Ctx, mod, gw: Tensor, g: Tensor, datas: Sequence[Tensor]) -> None:
+    """The weight gradient (of one source: on its dense form; of several: written per source into its channel range of the layer's
+    [Cout, Cin, k, k] gradient, or from their cat) and the bias gradient, added into the flat gradient buffer."""
+    KH, KW, st, pd, swapped = _wgrad_geometry(mod)
+    if len(datas) > 1 and WGRAD_PER_SOURCE:
+        off = 0
+        for d in datas:
+            K.conv_wgrad_src(g, d, gw, off, KH, KW, st, pd)
+            off += d.shape[1]
+    else:
+        xs = _dense(datas[0]) if len(datas) == 1 else _cat(datas)
+        if swapped:
+            K.conv_wgrad(xs, g, gw, KH, KW, st, pd)             # roles swapped: result is [Cin][Cout][k][k]
+        else:
+            K.conv_wgrad(g, xs, gw, KH, KW, st, pd)
+    gb = ctx.pgrad(mod.bias)
+    if gb is not None:
+        K.sum_rows(K.chan_reduce(g), gb, accumulate=True)
+
+
+def conv(ctx: Ctx, x: Union[Var, Sequence[Var]], mod, act: int = ops.ACT_NONE, out: Optional[Tensor] = None, res: Optional[Var] = None,
+         init: Optional[Var] = None) -> Var:
+    """Conv2d / ConvTranspose2d / Linear stand-ins of dc_vic_amd.layers; bias and (optionally) ReLU / LeakyReLU / 0.5 tanh fused forward;
+    `out`: a destination view, e.g. one half of the hyper-decoder's output.
+    A plain Conv2d also reads the channel concatenation of several Vars (views welcome: each with its own batch stride), never
+    materialised: act(conv(cat x) [+ init] + bias) [+ res].  One data gradient over all input channels, whose channel ranges are added to
+    the sources that need one (a constant source -- the one-hot VQ feature -- takes none), and one weight gradient."""
     if act not in _DIFF_ACTS:
         raise ValueError("only activations whose derivative follows from the output (ReLU, LeakyReLU, 0.5 tanh) may be fused into a differentiable conv")
     if act != ops.ACT_NONE and res is not None:
         raise ValueError("conv_multi: the residual is added after the activation, whose derivative is then not a function of the output")
-    if not isinstance(mod, Conv2d) or mod.upsample or mod.asym_pad:
+    srcs = [x] if isinstance(x, Var) else list(x)
+    ups = isinstance(mod, Conv2d) and mod.upsample
+    if (len(srcs) != 1 or res is not None or init is not None) and (not isinstance(mod, Conv2d) or ups or mod.asym_pad):
         raise NotImplementedError("conv_multi: plain Conv2d layers only")
     if not 1 <= len(srcs) <= ops.L.MAX_SRC:
         raise ValueError(f"conv_multi: 1..{ops.L.MAX_SRC} sources, got {len(srcs)}")
     chans = [int(v.shape[1]) for v in srcs]
-    if sum(chans) != mod.in_channels:
+    if isinstance(mod, Conv2d) and sum(chans) != mod.in_channels:
         raise ValueError(f"conv_multi: sources hold {chans} channels, the layer reads {mod.in_channels}")
     if any(v.needs_grad for v in srcs):
         _check_s2_input(mod, srcs[0].shape[2], srcs[0].shape[3])
     gw = ctx.pgrad(mod.weight)
     trainable = gw is not None
-    if trainable:            # the weights move every step: never reuse a cached pack
-        plan = ops.ConvPlan(mod.weight, mod.bias, "conv", stride=mod.stride, pad=(mod.padding, mod.padding))
-    else:
-        plan = mod._get_plan(bf16=False)
-    datas = [v.data for v in srcs]
-    y = plan(datas, act=act, res=res.data if res is not None else None, init=init.data if init is not None else None)
-    out = Var(y)
+    datas = [K.resample2(_dense(srcs[0].data), down=False)] if ups else [v.data for v in srcs]
+    y = _forward_plan(mod, trainable, ups)(datas, act=act, out=out, res=res.data if res is not None else None,
+                                           init=init.data if init is not None else None)
 
-    def back():
-        g = out.grad
-        if g is None:
-            return
+    def backward(g):
         g = _dense(g)
         if res is not None:
             acc(res, g)
         if act != ops.ACT_NONE:
-            g = K.ew(0, g, y, act=act)
+            g = K.ew(K.EW_ACT_GRAD, g, _dense(y), act=act)
         if init is not None:
             acc(init, g)
         if any(v.needs_grad for v in srcs):
-            cached = getattr(mod, "_dgrad", None)
-            dp = cached[1] if (not trainable and cached is not None and cached[0] == mod._key()) else None
-            if dp is None:
-                dp = _dgrad_plan(mod)
-                if not trainable:
-                    mod._dgrad = (mod._key(), dp)
-            dx = dp(g)
-            off = 0
-            for v, c in zip(srcs, chans):
-                if v.needs_grad:
-                    acc(v, _dense(dx[:, off:off + c]))
-                off += c
+            dx = _cached(mod, "_dgrad", trainable, lambda: _dgrad_plan(mod))(g)
+            _hand_out(K.resample2(dx, down=True) if ups else dx, srcs)
         if trainable:
-            k, st, pd = mod.kernel_size, mod.stride, mod.padding
-            if WGRAD_PER_SOURCE:
-                off = 0
-                for d, c in zip(datas, chans):
-                    K.conv_wgrad_src(g, d, gw, off, k, k, st, pd)
-                    off += c
-            else:
-                N, _, H, W = datas[0].shape
-                xs = torch.empty((N, sum(chans), H, W), dtype=torch.float32, device=g.device)
-                off = 0
-                for d, c in zip(datas, chans):
-                    ops.copy_planes(xs[:, off:off + c], d, H, W)
-                    off += c
-                K.conv_wgrad(g, xs, gw, k, k, st, pd)
-            gb = ctx.pgrad(mod.bias)
-            if gb is not None:
-                K.sum_rows(K.chan_reduce(g), gb, accumulate=True)
-    ctx.tape.append(back)
-    return out
+            _param_grads(ctx, mod, gw, g, datas)
+    return ctx.op(y, backward)
+
+
+conv_multi = conv       # the name the several-source form had as a function of its own
 
 
 # ------------------------------------------------------------------------------------------- normalisation
 def group_norm(ctx: Ctx, x: Var, mod: GroupNorm, act: int = ops.ACT_NONE) -> Var:
     xd = x.data
-    y = ops.groupnorm(xd, mod.weight, mod.bias, mod.num_groups, mod.eps, act)
-    out = Var(y)
 
-    def back():
-        if out.grad is None:
-            return
-        dx, dg, db = K.groupnorm_bwd(xd, out.grad, mod.weight, mod.bias, mod.num_groups, mod.eps, act)
+    def backward(g):
+        dx, dg, db = K.groupnorm_bwd(xd, g, mod.weight, mod.bias, mod.num_groups, mod.eps, act)
         acc(x, dx)
         gw, gb = ctx.pgrad(mod.weight), ctx.pgrad(mod.bias)
         if gw is not None:
             K.sum_rows(dg, gw, accumulate=True)
             K.sum_rows(db, gb, accumulate=True)
-    ctx.tape.append(back)
-    return out
+    return ctx.op(ops.groupnorm(xd, mod.weight, mod.bias, mod.num_groups, mod.eps, act), backward)
 
 
 def layer_norm_c(ctx: Ctx, x: Var, mod: LayerNormC) -> Var:
     xd = _dense(x.data)
-    y = ops.layernorm_c(xd, mod.weight, mod.bias, mod.eps)
-    out = Var(y)
 
-    def back():
-        if out.grad is None:
-            return
-        dx, part = K.layernorm_c_bwd(xd, _dense(out.grad), mod.weight, mod.eps)
+    def backward(g):
+        dx, part = K.layernorm_c_bwd(xd, _dense(g), mod.weight, mod.eps)
         acc(x, dx)
         gw, gb = ctx.pgrad(mod.weight), ctx.pgrad(mod.bias)
         if gw is not None:
             Cc = xd.shape[1]
             tmp = torch.empty(2 * Cc, dtype=torch.float32, device=xd.device)
             K.sum_rows(part, tmp, accumulate=False)
-            K.ew(10, None, gw, tmp[:Cc], out=gw)
-            K.ew(10, None, gb, tmp[Cc:], out=gb)
-    ctx.tape.append(back)
-    return out
+            K.ew(K.EW_ADD, None, gw, tmp[:Cc], out=gw)
+            K.ew(K.EW_ADD, None, gb, tmp[Cc:], out=gb)
+    return ctx.op(ops.layernorm_c(xd, mod.weight, mod.bias, mod.eps), backward)
 
 
 # ------------------------------------------------------------------------------------------- elementwise
 def activation(ctx: Ctx, x: Var, act: int) -> Var:
     xd = _dense(x.data)
     y = ops.activation(xd, act)
-    out = Var(y)
     ref = xd if act in (ops.ACT_SWISH, ops.ACT_GELU) else y
-
-    def back():
-        if out.grad is not None:
-            acc(x, K.ew(0, _dense(out.grad), ref, act=act))
-    ctx.tape.append(back)
-    return out
+    return ctx.op(y, lambda g: acc(x, K.ew(K.EW_ACT_GRAD, _dense(g), ref, act=act)))
 
 
-def add(ctx: Ctx, a: Var, b: Var) -> Var:
-    out = Var(ops.add(_dense(a.data), _dense(b.data)))
-
-    def back():
-        if out.grad is not None:
-            acc(a, out.grad)
-            acc(b, out.grad)
-    ctx.tape.append(back)
-    return out
+def add(ctx: Ctx, a: Var, b: Var, out: Optional[Tensor] = None) -> Var:
+    """a + b; `out`: a destination view (one CHARM slice of the y_hat buffer)."""
+    def backward(g):
+        acc(a, g)
+        acc(b, g)
+    return ctx.op(ops.add(_dense(a.data), _dense(b.data), out=out), backward)
 
 
 def nlam_gate(ctx: Ctx, x: Var, t: Var, a: Var) -> Var:
     """x + t * sigmoid(a)   (ChengNLAM, cheng_nlam.py:23-27)."""
     xd, td, ad = _dense(x.data), _dense(t.data), _dense(a.data)
-    out = Var(ops.add_mul_sigmoid(xd, td, ad))
 
-    def back():
-        g = out.grad
-        if g is None:
-            return
+    def backward(g):
         g = _dense(g)
         acc(x, g)
-        acc(t, K.ew(2, g, ad))
-        acc(a, K.ew(3, g, td, ad))
-    ctx.tape.append(back)
-    return out
+        acc(t, K.ew(K.EW_MUL_SIGMOID, g, ad))
+        acc(a, K.ew(K.EW_MUL_DSIGMOID, g, td, ad))
+    return ctx.op(ops.add_mul_sigmoid(xd, td, ad), backward)
 
 
 def sft(ctx: Ctx, dec: Var, scale: Var, shift: Var, w: float = 1.0) -> Var:
     """dec + w * (dec * scale + shift)   (FuseSftBlock, codeformer_layers.py:65-66)."""
     dd, sd, hd = _dense(dec.data), _dense(scale.data), _dense(shift.data)
-    out = Var(ops.sft(dd, sd, hd, w=w))
 
-    def back():
-        g = out.grad
-        if g is None:
-            return
+    def backward(g):
         g = _dense(g)
-        acc(dec, K.ew(4, g, sd, w=w))
-        acc(scale, K.ew(5, g, dd, w=w))
-        acc(shift, K.ew(6, g, w=w))
-    ctx.tape.append(back)
-    return out
+        acc(dec, K.ew(K.EW_SFT_DEC, g, sd, w=w))
+        acc(scale, K.ew(K.EW_SFT_SCALE, g, dd, w=w))
+        acc(shift, K.ew(K.EW_SFT_SHIFT, g, w=w))
+    return ctx.op(ops.sft(dd, sd, hd, w=w), backward)
 
 
 def chan_affine(ctx: Ctx, x: Var, s: Var, t: Var, add_x: bool = False) -> Var:
@@ -427,17 +408,13 @@ def chan_affine(ctx: Ctx, x: Var, s: Var, t: Var, add_x: bool = False) -> Var:
     xd = _dense(x.data)
     N, Cc = xd.shape[:2]
     sv, tv = s.data.reshape(s.data.shape[0], Cc).contiguous(), t.data.reshape(t.data.shape[0], Cc).contiguous()
-    out = Var(ops.chan_affine(xd, sv, tv, add_=xd if add_x else None))
 
-    def back():
-        g = out.grad
-        if g is None:
-            return
+    def backward(g):
         g = _dense(g)
         if x.needs_grad:
-            dx = K.ew(7, g, sv, vec_bs=Cc if sv.shape[0] > 1 else 0)
+            dx = K.ew(K.EW_CHAN_SCALE, g, sv, vec_bs=Cc if sv.shape[0] > 1 else 0)
             if add_x:
-                dx = K.ew(10, None, dx, g)
+                dx = K.ew(K.EW_ADD, None, dx, g)
             acc(x, dx)
         ds, dt = K.chan_reduce(g, xd), K.chan_reduce(g)                   # [N, C]
         if sv.shape[0] == 1:
@@ -447,41 +424,11 @@ def chan_affine(ctx: Ctx, x: Var, s: Var, t: Var, add_x: bool = False) -> Var:
             ds, dt = ds1, dt1
         acc(s, ds.view(s.data.shape))
         acc(t, dt.view(t.data.shape))
-    ctx.tape.append(back)
-    return out
+    return ctx.op(ops.chan_affine(xd, sv, tv, add_=xd if add_x else None), backward)
 
 
 def upsample2(ctx: Ctx, x: Var) -> Var:
-    out = Var(K.resample2(_dense(x.data), down=False))
-
-    def back():
-        if out.grad is not None:
-            acc(x, K.resample2(_dense(out.grad), down=True))
-    ctx.tape.append(back)
-    return out
-
-
-def cat_channels(ctx: Ctx, parts: Sequence[Var]) -> Var:
-    N, _, H, W = parts[0].shape
-    Ct = sum(p.shape[1] for p in parts)
-    buf = torch.empty((N, Ct, H, W), dtype=torch.float32, device=parts[0].data.device)
-    off = 0
-    offs = []
-    for p in parts:
-        c = p.shape[1]
-        ops.copy_planes(buf[:, off:off + c], p.data, H, W)
-        offs.append((off, c))
-        off += c
-    out = Var(buf)
-
-    def back():
-        if out.grad is None:
-            return
-        for p, (o, c) in zip(parts, offs):
-            if p.needs_grad:
-                acc(p, _dense(out.grad[:, o:o + c]))
-    ctx.tape.append(back)
-    return out
+    return ctx.op(K.resample2(_dense(x.data), down=False), lambda g: acc(x, K.resample2(_dense(g), down=True)))
 
 
 # ------------------------------------------------------------------------------------------- attention
@@ -491,13 +438,9 @@ def attn_single_head(ctx: Ctx, qkv: Var, Cc: int) -> Var:
     qd = _dense(qkv.data)
     N, _, H, W = qd.shape
     HW = H * W
-    out = Var(ops.attn_fused(qd, Cc))
     scale = float(int(Cc) ** (-0.5))
 
-    def back():
-        g = out.grad
-        if g is None:
-            return
+    def backward(g):
         g = _dense(g)                                              # dO [N, C, HW]
         bs = 3 * Cc * HW
         q, k, v = qd[:, :Cc], qd[:, Cc:2 * Cc], qd[:, 2 * Cc:]
@@ -516,22 +459,17 @@ def attn_single_head(ctx: Ctx, qkv: Var, Cc: int) -> Var:
         ops.bgemm(k, (bs, HW, 1), dS, (HW * HW, HW, 1), dq, (bs, HW), N, Cc, HW, HW)
         ops.bgemm(q, (bs, HW, 1), dS, (HW * HW, 1, HW), dk, (bs, HW), N, Cc, HW, HW)
         acc(qkv, dqkv)
-    ctx.tape.append(back)
-    return out
+    return ctx.op(ops.attn_fused(qd, Cc), backward)
 
 
 def swin_attention(ctx: Ctx, qkv: Var, table: nn.Parameter, heads: int, ws: int, shift: int) -> Var:
     qd = _dense(qkv.data)
-    out = Var(ops.swin_attn(qd, table, heads, ws, shift))
 
-    def back():
-        if out.grad is None:
-            return
+    def backward(g):
         gt = ctx.pgrad(table)
         dt = gt if gt is not None else torch.zeros_like(table)
-        acc(qkv, K.swin_attn_bwd(qd, _dense(out.grad), table, dt, heads, ws, shift, accumulate=gt is not None))
-    ctx.tape.append(back)
-    return out
+        acc(qkv, K.swin_attn_bwd(qd, _dense(g), table, dt, heads, ws, shift, accumulate=gt is not None))
+    return ctx.op(ops.swin_attn(qd, table, heads, ws, shift), backward)
 
 
 # ------------------------------------------------------------------------------------------- losses (seed the gradients)
@@ -539,8 +477,8 @@ def mse_loss(ctx: Ctx, a: Var, target: Tensor, weight: float) -> Tensor:
     """weight * mean((a - target)^2): value as a 1-element device tensor, gradient seeded into `a`."""
     ad, td = _dense(a.data), _dense(target)
     n = ad.numel()
-    val = K.reduce_loss(0, ad, td, weight / n)
-    acc(a, K.ew(8, None, ad, td, w=weight / n))
+    val = K.reduce_loss(K.SUM_SQ_ERR, ad, td, weight / n)
+    acc(a, K.ew(K.EW_MSE_GRAD, None, ad, td, w=weight / n))
     return val
 
 
@@ -548,8 +486,8 @@ def bce_logits_loss(ctx: Ctx, x: Var, is_real: bool, weight: float) -> Tensor:
     """weight * BCEWithLogits(x, 1 or 0), mean reduction (src/losses/gan_loss.py:10-32)."""
     xd = _dense(x.data)
     n = xd.numel()
-    val = K.reduce_loss(1, xd, None, weight / n, target=1 if is_real else 0)
-    acc(x, K.ew(9, None, xd, w=weight / n, act=1 if is_real else 0))
+    val = K.reduce_loss(K.SUM_BCE, xd, None, weight / n, target=1 if is_real else 0)
+    acc(x, K.ew(K.EW_BCE_GRAD, None, xd, w=weight / n, act=1 if is_real else 0))
     return val
 
 
@@ -559,7 +497,7 @@ def cross_entropy_loss(ctx: Ctx, logits: Var, target: Tensor, weight: float) -> 
     N, Cc, H, W = ld.shape
     m = N * H * W
     nll, dl = K.cross_entropy(ld, target.contiguous(), weight / m, want_grad=True)
-    val = K.reduce_loss(3, nll, None, weight / m)
+    val = K.reduce_loss(K.SUM, nll, None, weight / m)
     acc(logits, dl)
     return val
 
@@ -598,7 +536,7 @@ def gaussian_rate(ctx: Ctx, y: Var, mu: Var, sigma: Var, noise: Tensor, weights:
     e.g. a CHARM slice of one 192-channel gradient) the gradient w.r.t. y is written there instead and the caller seeds the parent
     once; `lik_out` (a view too) takes the noisy likelihoods.  Returns y_hat = ste_round(y - mu) + mu: a gradient arriving on it goes to `y` unchanged and not to `mu`."""
     new = lambda: torch.empty(y.shape, dtype=torch.float32, device=y.data.device)
-    out = Var(new(), needs_grad=y.needs_grad)
+    out = ctx.op(new(), lambda g: acc(y, g), needs_grad=y.needs_grad)
     dy = dy_out if dy_out is not None else (new() if y.needs_grad else None)
     dmu, dsigma = (new() if mu.needs_grad else None), (new() if sigma.needs_grad else None)
     K.gaussian_rate_train(y.data, mu.data, sigma.data, noise, weights, scale, y_hat=out.data, lik=lik_out, bits=bits, loss=loss, dy=dy,
@@ -609,11 +547,6 @@ def gaussian_rate(ctx: Ctx, y: Var, mu: Var, sigma: Var, noise: Tensor, weights:
         acc(mu, dmu)
     if dsigma is not None:
         acc(sigma, dsigma)
-
-    def back():
-        if out.grad is not None:
-            acc(y, out.grad)
-    ctx.tape.append(back)
     return out
 
 
@@ -623,7 +556,7 @@ def eb_rate(ctx: Ctx, z: Var, eb, noise: Tensor, weights: Optional[Tensor], scal
     loss term's gradient is seeded into `z` and, when `eb`'s parameters belong to one of ctx's groups, added to their views of the flat
     gradient buffer.  Returns z_hat = ste_round(z - medians) + medians: its gradient goes to `z` unchanged, none to the medians."""
     zd = _dense(z.data)
-    out = Var(torch.empty_like(zd), needs_grad=z.needs_grad)
+    out = ctx.op(torch.empty_like(zd), lambda g: acc(z, g), needs_grad=z.needs_grad)
     grads = [ctx.pgrad(getattr(eb, name)) for name in K.EB_PARAM_NAMES]
     grads = None if any(g is None for g in grads) else grads
     dz = torch.empty_like(zd) if z.needs_grad else None
@@ -631,11 +564,6 @@ def eb_rate(ctx: Ctx, z: Var, eb, noise: Tensor, weights: Optional[Tensor], scal
                     dz=dz, grads=grads)
     if dz is not None:
         acc(z, dz)
-
-    def back():
-        if out.grad is not None:
-            acc(z, out.grad)
-    ctx.tape.append(back)
     return out
 
 

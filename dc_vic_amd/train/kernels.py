@@ -70,12 +70,33 @@ def sum_rows(x: Tensor, out: Tensor, accumulate: bool) -> None:
     check(lib().dcvic_sum_rows_f32(_p(x), _p(out), rows, ln, 1 if accumulate else 0, _stream()), "sum_rows")
 
 
+# The `op` of ew (dcvic_ew_bwd_f32); the table above ew_bwd_kernel in csrc/train.hip is the authority.
+EW_ACT_GRAD = 0         # d = g * act'(a)              a: the OUTPUT for relu / lrelu02 / sigmoid / half_tanh, the INPUT for swish / gelu
+EW_MUL = 1              # d = g * a
+EW_MUL_SIGMOID = 2      # d = g * sigmoid(a)
+EW_MUL_DSIGMOID = 3     # d = g * a * s (1 - s), s = sigmoid(b)
+EW_SFT_DEC = 4          # d = g * (1 + w * a)
+EW_SFT_SCALE = 5        # d = w * g * a
+EW_SFT_SHIFT = 6        # d = w * g
+EW_CHAN_SCALE = 7       # d = g * (1 + a[n][c])        a: a per-channel vector [N or 1][C], vec_bs = C or 0
+EW_MSE_GRAD = 8         # d = 2 * w * (a - b)
+EW_BCE_GRAD = 9         # d = w * (sigmoid(a) - act)   act: the target, 0 or 1
+EW_ADD = 10             # d = a + b
+EW_SCALE = 11           # d = a * w
+
+# The `kind` of reduce_loss (dcvic_reduce_loss_f32, csrc/train.hip): out = scale * sum_i f.
+SUM_SQ_ERR = 0          # f = (a - b)^2
+SUM_BCE = 1             # f = BCE-with-logits(a, target)
+SUM_SQ = 2              # f = a^2
+SUM = 3                 # f = a
+
+
 def ew(op: int, g: Optional[Tensor], a: Optional[Tensor] = None, b: Optional[Tensor] = None, w: float = 1.0, act: int = 0,
        out: Optional[Tensor] = None, vec_bs: int = 0) -> Tensor:
     ref = g if g is not None else a
     if out is None:
         out = torch.empty(ref.shape, dtype=torch.float32, device=ref.device)
-    for t in (g, a if op != 7 else None, b, out):
+    for t in (g, a if op != EW_CHAN_SCALE else None, b, out):
         if t is not None and not t.is_contiguous():
             raise ValueError("ew_bwd operands must be contiguous")
     Cc = ref.shape[1] if ref.dim() == 4 else 1

@@ -85,16 +85,13 @@ def s2d(ctx: Ctx, x: Var, r: int, pad: int, k: int) -> Var:
     Ho, Wo = (H + 2 * pad - k) // r + 1 + (k - 1) // r, (W + 2 * pad - k) // r + 1 + (k - 1) // r
     y = torch.empty((N, Cc * r * r, Ho, Wo), dtype=torch.float32, device=xd.device)
     check(lib().dcvic_s2d_f32(_p(xd), _p(y), N * Cc, H, W, r, pad, Ho, Wo, 0, _stream()), "s2d")
-    out = Var(y)
 
-    def back():
-        if out.grad is None or not x.needs_grad:
-            return
-        dx = torch.empty_like(xd)
-        check(lib().dcvic_s2d_f32(_p(A._dense(out.grad)), _p(dx), N * Cc, H, W, r, pad, Ho, Wo, 1, _stream()), "s2d_bwd")
-        A.acc(x, dx)
-    ctx.tape.append(back)
-    return out
+    def backward(g):
+        if x.needs_grad:
+            dx = torch.empty_like(xd)
+            check(lib().dcvic_s2d_f32(_p(A._dense(g)), _p(dx), N * Cc, H, W, r, pad, Ho, Wo, 1, _stream()), "s2d_bwd")
+            A.acc(x, dx)
+    return ctx.op(y, backward)
 
 
 def maxpool3s2(ctx: Ctx, x: Var) -> Var:
@@ -104,16 +101,13 @@ def maxpool3s2(ctx: Ctx, x: Var) -> Var:
     y = torch.empty((N, Cc, Ho, Wo), dtype=torch.float32, device=xd.device)
     am = torch.empty((N, Cc, Ho, Wo), dtype=torch.uint8, device=xd.device)
     check(lib().dcvic_maxpool3s2_f32(_p(xd), _p(y), _p(am), None, None, N * Cc, H, W, _stream()), "maxpool")
-    out = Var(y)
 
-    def back():
-        if out.grad is None or not x.needs_grad:
-            return
-        dx = torch.empty_like(xd)
-        check(lib().dcvic_maxpool3s2_f32(None, None, _p(am), _p(A._dense(out.grad)), _p(dx), N * Cc, H, W, _stream()), "maxpool_bwd")
-        A.acc(x, dx)
-    ctx.tape.append(back)
-    return out
+    def backward(g):
+        if x.needs_grad:
+            dx = torch.empty_like(xd)
+            check(lib().dcvic_maxpool3s2_f32(None, None, _p(am), _p(A._dense(g)), _p(dx), N * Cc, H, W, _stream()), "maxpool_bwd")
+            A.acc(x, dx)
+    return ctx.op(y, backward)
 
 
 def features(ctx: Ctx, L: LPIPSAlex, img: Var) -> List[Var]:
@@ -145,6 +139,6 @@ def lpips_loss(ctx: Ctx, L: LPIPSAlex, real: Tensor, fake: Var, weight: float) -
         df1 = torch.empty_like(f1d)
         check(lib().dcvic_lpips_tap_f32(_p(f0), _p(f1d), _p(w), _p(pix), _p(df1), N, Cc, H * W, weight / N, _stream()), "lpips_tap")
         A.acc(f1, df1)
-        v = K.reduce_loss(3, pix, None, weight / (N * H * W))
-        total = v if total is None else K.ew(10, None, total, v)
+        v = K.reduce_loss(K.SUM, pix, None, weight / (N * H * W))
+        total = v if total is None else K.ew(K.EW_ADD, None, total, v)
     return total

@@ -110,7 +110,7 @@ def encoder_forward(ctx: Ctx, enc, x: Tensor, feat: Tensor, beta_1, beta_2) -> V
     h = ft(3, bottleneck_blocks(ctx, enc.block2, h))
     h = ft(4, nlam(ctx, enc.attn2, h))
     h = ft(5, A.conv(ctx, h, enc.conv3))
-    h = A.conv_multi(ctx, [A.const(feat), h], enc.projection, res=h)          # x + conv3x3(cat[feat, x])   (:131-132)
+    h = A.conv(ctx, [A.const(feat), h], enc.projection, res=h)          # x + conv3x3(cat[feat, x])   (:131-132)
     h = ft(6, bottleneck_blocks(ctx, enc.block3, h))
     h = ft(7, A.conv(ctx, h, enc.conv4))
     return ft(8, nlam(ctx, enc.attn4, h))
@@ -123,7 +123,7 @@ def hyper_encoder_forward(ctx: Ctx, he, y: Var) -> Var:
 
 
 def hyper_decoder_forward(ctx: Ctx, hd, z_hat: Var) -> Var:
-    """Minnen20HyperDecoder.forward: the two branches write the halves of ONE hyper_out; its gradient is handed to them as views."""
+    """Minnen20HyperDecoder.forward: the two branches write the halves of ONE hyper_out."""
     N, _, H, W = z_hat.shape
     half = hd.half
     buf = torch.empty((N, 2 * half, 4 * H, 4 * W), dtype=torch.float32, device=z_hat.data.device)
@@ -132,18 +132,11 @@ def hyper_decoder_forward(ctx: Ctx, hd, z_hat: Var) -> Var:
         h = A.conv(ctx, z_hat, blk.conv1, act=ops.ACT_RELU)
         h = A.conv(ctx, h, blk.conv2, act=ops.ACT_RELU)
         outs.append(A.conv(ctx, h, blk.conv3, out=dst))
-    hyper_out = Var(buf)
-
-    def back():
-        if hyper_out.grad is not None:
-            A.acc(outs[0], hyper_out.grad[:, :half])
-            A.acc(outs[1], hyper_out.grad[:, half:])
-    ctx.tape.append(back)
-    return hyper_out
+    return A.join_channels(ctx, buf, outs)
 
 
 def _slice_transform(ctx: Ctx, st, srcs, act: int = ops.ACT_NONE) -> Var:
-    h = A.conv_multi(ctx, srcs, st.model[0], act=ops.ACT_RELU)
+    h = A.conv(ctx, srcs, st.model[0], act=ops.ACT_RELU)
     h = A.conv(ctx, h, st.model[2], act=ops.ACT_RELU)
     return A.conv(ctx, h, st.model[4], act=act)
 
@@ -164,37 +157,15 @@ def charm_forward_train(ctx: Ctx, cm, y: Var, hyper_out: Var, entropy_model_y, n
     new = lambda dtype=torch.float32: torch.empty((N, Cy, H, W), dtype=dtype, device=dev)
     y_hat_buf, dy_rate, lik, q_lik, sym = new(), new(), new(), new(), new(torch.int32)
     table = entropy_model_y._table_dev(y.data)
-    h_mean, h_scale = Var(hyper_out.data[:, :hm], hyper_out.needs_grad), Var(hyper_out.data[:, hm:], hyper_out.needs_grad)
-    y_sl = [Var(y.data[:, i * sc:(i + 1) * sc], y.needs_grad) for i in range(ns)]
+    # split_channels records its gather now, so it runs after every slice's backward (of y last: hyper_out's runs first)
+    y_sl = A.split_channels(ctx, y, [sc] * ns)
+    h_mean, h_scale = A.split_channels(ctx, hyper_out, [hm, hm])
     yh_sl = []
-
-    def back_inputs():                                   # appended first: runs after every slice's backward
-        if hyper_out.needs_grad and (h_mean.grad is not None or h_scale.grad is not None):
-            dh = torch.zeros(hyper_out.shape, dtype=torch.float32, device=dev)
-            if h_mean.grad is not None:
-                ops.copy_planes(dh[:, :hm], h_mean.grad, H, W)
-            if h_scale.grad is not None:
-                ops.copy_planes(dh[:, hm:], h_scale.grad, H, W)
-            A.acc(hyper_out, dh)
-        if y.needs_grad:
-            ste = torch.zeros(y.shape, dtype=torch.float32, device=dev)
-            for i, v in enumerate(y_sl):
-                if v.grad is not None:
-                    ops.copy_planes(ste[:, i * sc:(i + 1) * sc], v.grad, H, W)
-            A.acc(y, A.K.ew(10, None, dy_rate, ste))          # rate gradient (seeded at forward time) + what came through the STE
-    ctx.tape.append(back_inputs)
-
     for i in range(ns):
         sl = slice(i * sc, (i + 1) * sc)
         k = cm._n_support(i)
-        sup = Var(y_hat_buf[:, :k * sc]) if k > 0 else None
-        if sup is not None:
-            def back_support(sup=sup, k=k):              # after this slice's three transforms: hand the support's gradient to its slices
-                if sup.grad is not None:
-                    for j in range(k):
-                        A.acc(yh_sl[j], A._dense(sup.grad[:, j * sc:(j + 1) * sc]))
-            ctx.tape.append(back_support)
-        support = [sup] if sup is not None else []
+        # the support's join is recorded before this slice's three transforms: it hands their gradients on to the earlier slices after them
+        support = [A.join_channels(ctx, y_hat_buf[:, :k * sc], yh_sl[:k])] if k > 0 else []
         mu = _slice_transform(ctx, cm.mean_slice_transforms[i], [h_mean] + support)
         sigma = _slice_transform(ctx, cm.scale_slice_transforms[i], [h_scale] + support)
         yq = A.gaussian_rate(ctx, y_sl[i], mu, sigma, noise[:, sl], weights, scale, bits, loss, dy_out=dy_rate[:, sl] if y.needs_grad else None,
@@ -202,22 +173,9 @@ def charm_forward_train(ctx: Ctx, cm, y: Var, hyper_out: Var, entropy_model_y, n
         # the quantised likelihood (no gradient): the eval kernel on the same mu / sigma
         ops.gaussian_rate(y_sl[i].data, None, mu.data, sigma.data, table, None, sym[:, sl], None, q_lik[:, sl], q_bits)
         lrp = _slice_transform(ctx, cm.lrp_slice_transforms[i], [h_mean] + support + [yq], act=ops.ACT_HALF_TANH)
-        ops.add(yq.data, lrp.data, out=y_hat_buf[:, sl])
-        yh = Var(y_hat_buf[:, sl])
-        yh_sl.append(yh)
-
-        def back_add(yh=yh, yq=yq, lrp=lrp):
-            if yh.grad is not None:
-                A.acc(yq, yh.grad)
-                A.acc(lrp, yh.grad)
-        ctx.tape.append(back_add)
-    y_hat = Var(y_hat_buf)
-
-    def back_out():                                      # appended last: runs first
-        if y_hat.grad is not None:
-            for i in range(ns):
-                A.acc(yh_sl[i], A._dense(y_hat.grad[:, i * sc:(i + 1) * sc]))
-    ctx.tape.append(back_out)
+        yh_sl.append(A.add(ctx, yq, lrp, out=y_hat_buf[:, sl]))
+    A.acc(y, dy_rate)            # the rate gradient, seeded at forward time; what comes through the STE is added by y's split_channels
+    y_hat = A.join_channels(ctx, y_hat_buf, yh_sl)
     return dict(y_hat=y_hat, likelihood=lik, q_likelihood=q_lik, symbols=sym)
 
 

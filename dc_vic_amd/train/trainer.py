@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..layers import invalidate_weight_caches
 from ..registry import LOSS_REGISTRY, TRAINER_REGISTRY
 from . import autograd as A
 from . import kernels as K
@@ -54,7 +55,7 @@ def allreduce_mean_(flat: Tensor, dist, bucket_bytes: int = 64 << 20) -> int:
     for w in works:
         w.wait()
     if flat.is_cuda:
-        K.ew(11, None, flat, w=1.0 / dist.get_world_size(), out=flat)
+        K.ew(K.EW_SCALE, None, flat, w=1.0 / dist.get_world_size(), out=flat)
     else:
         flat.mul_(1.0 / dist.get_world_size())        # CPU (gloo tests): plumbing only
     return len(works)
@@ -156,9 +157,7 @@ class DualBetaCondGanDistortionVqCodeTrainer:
             if tuple(sd[k].shape) != tuple(v.shape):
                 raise ValueError(f"lpips state dict: {k} has shape {tuple(sd[k].shape)}, expected {tuple(v.shape)}")
             v.copy_(sd[k].to(v.device, dtype=v.dtype))
-        for m in self.lpips.modules():
-            if hasattr(m, "_plan"):
-                m._plan = None
+        invalidate_weight_caches(self.lpips)
         self.lpips_is_synthetic = False
 
     # ---------------------------------------------------------------- training state (base_trainer.py:178-214 saves optimizer + scheduler state)
@@ -292,7 +291,7 @@ class DualBetaCondGanDistortionVqCodeTrainer:
         allreduce_mean_(self.g_group.grad, self.dist)
         gscale = None
         if self.clip:
-            gscale = K.clip_scale(K.reduce_loss(2, self.g_group.grad, None, 1.0), self.clip)
+            gscale = K.clip_scale(K.reduce_loss(K.SUM_SQ, self.g_group.grad, None, 1.0), self.clip)
         self.g_opt.step(self.g_sched.lr(), gscale)
         self._drop_inference_graphs()
         lr_now = self.g_sched.lr()

@@ -164,6 +164,141 @@ def test_gates_and_affine_backward():
     relclose(xv.grad, g3[:, :16] + g3[:, 32:], 2e-5, "cat fan-out"); relclose(tv.grad, g3[:, 16:32], 2e-5, "cat middle")
 
 
+# ------------------------------------------------------------------------------------------------ the tape's frame and its channel views
+# These move data (or add once in fp32, which the CPU does to the same bits): torch.equal against torch slicing, cat and + on the CPU.
+# The 3 x 5 plane keeps copy_planes off any float4 path.
+def _nan_buffer(*shape):
+    return torch.full(shape, float("nan"), device=DEV)
+
+
+@pytest.mark.parametrize("seeded", ["both", "second", "neither"])
+@pytest.mark.parametrize("parent", ["dense", "view"])
+def test_split_channels(parent, seeded):
+    """The parent's gradient is the cat of the views' gradients (zeros for a view that received none, None if none did), added to what
+    the parent held before; the parent dense, or a channel-slice view with its own batch stride."""
+    from dc_vic_amd.train import autograd as A
+    x, g0, g1, pre = rnd(2, 7, 3, 5, seed=70), rnd(2, 3, 3, 5, seed=71), rnd(2, 4, 3, 5, seed=72), rnd(2, 7, 3, 5, seed=73)
+    if parent == "dense":
+        xd = x.to(DEV)
+    else:
+        big = _nan_buffer(2, 11, 3, 5)
+        big[:, 2:9] = x.to(DEV)
+        xd = big[:, 2:9]
+    gathered = None if seeded == "neither" else torch.cat([g0 if seeded == "both" else torch.zeros_like(g0), g1], 1)
+    for with_pre in (False, True):
+        ctx = A.Ctx([])
+        pv = A.Var(xd)
+        v0, v1 = A.split_channels(ctx, pv, (3, 4))
+        assert v0.needs_grad and v1.needs_grad and v0.data.data_ptr() == xd.data_ptr()
+        assert torch.equal(v0.data.cpu(), x[:, :3]) and torch.equal(v1.data.cpu(), x[:, 3:])
+        if with_pre:
+            A.acc(pv, pre.to(DEV))
+        if seeded == "both":
+            v0.grad = g0.to(DEV)
+        if seeded != "neither":
+            v1.grad = g1.to(DEV)
+        ctx.backward()
+        if gathered is None:
+            assert (pv.grad is None) if not with_pre else torch.equal(pv.grad.cpu(), pre)
+        else:
+            assert torch.equal(pv.grad.cpu(), pre + gathered if with_pre else gathered), (parent, seeded, with_pre)
+    assert not any(v.needs_grad for v in A.split_channels(A.Ctx([]), A.const(xd), (3, 4)))
+    with pytest.raises(ValueError, match="split_channels"):
+        A.split_channels(A.Ctx([]), A.Var(xd), (3, 3))
+
+
+def test_join_channels():
+    """Two parts written through `out=` into the slices (3, 4) of one buffer, the second a constant: the first takes its slice of the
+    joined Var's gradient as a dense copy of its own, the constant none."""
+    from dc_vic_amd import ops
+    from dc_vic_amd.train import autograd as A
+    a, b, c, g = rnd(2, 3, 3, 5, seed=74), rnd(2, 3, 3, 5, seed=75), rnd(2, 4, 3, 5, seed=76), rnd(2, 7, 3, 5, seed=77)
+    buf = _nan_buffer(2, 7, 3, 5)
+    ctx = A.Ctx([])
+    av, bv = A.Var(a.to(DEV)), A.Var(b.to(DEV))
+    p0 = A.add(ctx, av, bv, out=buf[:, :3])
+    p1 = A.const(ops.add(c.to(DEV), c.to(DEV), out=buf[:, 3:]))
+    joined = A.join_channels(ctx, buf, [p0, p1])
+    assert joined.data is buf and torch.equal(buf.cpu(), torch.cat([a + b, c + c], 1))
+    seed = g.to(DEV)
+    joined.grad = seed
+    ctx.backward()
+    assert torch.equal(p0.grad.cpu(), g[:, :3]) and p0.grad.is_contiguous()
+    assert p0.grad.untyped_storage().data_ptr() != seed.untyped_storage().data_ptr()
+    assert p1.grad is None
+    assert torch.equal(av.grad.cpu(), g[:, :3]) and torch.equal(bv.grad.cpu(), g[:, :3])
+    with pytest.raises(ValueError, match="join_channels"):
+        A.join_channels(A.Ctx([]), buf, [p0])
+
+
+def test_add_into_a_view():
+    from dc_vic_amd.train import autograd as A
+    a, b, g = rnd(2, 3, 3, 5, seed=78), rnd(2, 3, 3, 5, seed=79), rnd(2, 3, 3, 5, seed=80)
+    buf = _nan_buffer(2, 7, 3, 5)
+    ctx = A.Ctx([])
+    av, bv = A.Var(a.to(DEV)), A.Var(b.to(DEV))
+    out = A.add(ctx, av, bv, out=buf[:, 2:5])
+    assert out.data.data_ptr() == buf[:, 2:5].data_ptr() and tuple(out.shape) == (2, 3, 3, 5)
+    assert torch.equal(buf[:, 2:5].cpu(), a + b)
+    assert bool(torch.isnan(buf[:, :2]).all()) and bool(torch.isnan(buf[:, 5:]).all())          # the rest of the buffer is untouched
+    out.grad = g.to(DEV)
+    ctx.backward()
+    assert torch.equal(av.grad.cpu(), g) and torch.equal(bv.grad.cpu(), g)
+
+
+@pytest.mark.parametrize("source", ["dense", "view"])
+def test_conv_forms_give_the_same_bits(source):
+    """conv on a bare Var, on a one-element list and through the name conv_multi: the same output, data gradient and flat gradient,
+    bit for bit; the source dense, or a channel-slice view with its own batch stride."""
+    from dc_vic_amd.layers import Conv2d
+    from dc_vic_amd.train import autograd as A
+    x, g = rnd(2, 12, 4, 8, seed=81), rnd(2, 20, 4, 8, seed=82)
+    mod = Conv2d(12, 20, 3, 1, 1).to(DEV)
+    mod.weight.data.copy_(rnd(20, 12, 3, 3, seed=83, scale=0.1)); mod.bias.data.copy_(rnd(20, seed=84, scale=0.1))
+    grp = A.ParamGroup([mod], DEV)
+    if source == "dense":
+        xd = x.to(DEV)
+    else:
+        big = _nan_buffer(2, 20, 4, 8)
+        big[:, 4:16] = x.to(DEV)
+        xd = big[:, 4:16]
+    got = []
+    for form in ("bare", "list", "conv_multi"):
+        grp.zero_grad()
+        ctx = A.Ctx([grp])
+        xv = A.Var(xd)
+        out = A.conv(ctx, xv, mod) if form == "bare" else A.conv(ctx, [xv], mod) if form == "list" else A.conv_multi(ctx, [xv], mod)
+        out.grad = g.to(DEV)
+        ctx.backward()
+        got.append((out.data.cpu(), xv.grad.cpu(), grp.grad.cpu().clone()))
+    y = F.conv2d(x.double(), mod.weight.detach().cpu().double(), mod.bias.detach().cpu().double(), padding=1)
+    relclose(got[0][0], y, 1e-5, "forward")
+    assert float(got[0][1].abs().max()) > 0 and float(got[0][2].abs().max()) > 0
+    for other in got[1:]:
+        for t0, t1, what in zip(got[0], other, ("out", "dx", "flat gradient")):
+            assert torch.equal(t0, t1), what
+
+
+def test_ctx_op_frame():
+    """An op whose output never receives a gradient leaves its inputs alone; one that does gets that very tensor; backward() empties
+    the tape either way."""
+    from dc_vic_amd import ops
+    from dc_vic_amd.train import autograd as A
+    x = rnd(2, 4, 3, 5, seed=85).to(DEV)
+    ctx = A.Ctx([])
+    xv, seen = A.Var(x), []
+    A.activation(ctx, A.add(ctx, xv, xv), ops.ACT_RELU)
+    out = ctx.op(x, seen.append, needs_grad=False)
+    assert out.data is x and out.grad is None and not out.needs_grad and len(ctx.tape) == 3
+    ctx.backward()
+    assert xv.grad is None and seen == [] and ctx.tape == []
+    out = ctx.op(x, seen.append)
+    g = torch.ones_like(x)
+    out.grad = g
+    ctx.backward()
+    assert len(seen) == 1 and seen[0] is g and ctx.tape == []
+
+
 def test_attention_backward():
     from dc_vic_amd.train import autograd as A
     N, C, H, W = 2, 128, 8, 16

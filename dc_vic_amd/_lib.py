@@ -1,4 +1,4 @@
-"""ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h, include/dcvic_rate.h, include/dcvic_train.h).  The library is REQUIRED: there is no
+"""ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h, include/dcvic_rate.h, include/dcvic_train.h, include/dcvic_vq.h).  The library is REQUIRED: there is no
 fallback path -- if it is missing or an entry point fails, the caller gets an exception."""
 from __future__ import annotations
 
@@ -113,6 +113,11 @@ RATE_SIGNATURES = {
 TRAIN_SIGNATURES = {
     "dcvic_conv_wgrad_src_f32": "i:pqiiipqiiiiiiiiipiiipp",
 }
+# include/dcvic_vq.h: which search kernel dcvic_vq_argmin_f32 launched (csrc/vq.hip), and its codes
+VQ_SIGNATURES = {
+    "dcvic_vq_last_variant": "i:",
+}
+VQ_NONE, VQ_SHARD, VQ_PACKED2, VQ_PACKED1, VQ_LDS4, VQ_LDS8 = range(6)
 
 _lib = None
 
@@ -131,7 +136,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python dc_vic_amd/csrc/build.py` "
             "(or __graft_entry__.build()). dc_vic_amd has no fallback path.")
     L = C.CDLL(LIB_PATH)
-    for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items(), *RATE_SIGNATURES.items(), *TRAIN_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
+    for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items(), *RATE_SIGNATURES.items(), *TRAIN_SIGNATURES.items(), *VQ_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
         fn = getattr(L, name)                # AttributeError names a symbol the library lacks
         ret, params = sig.split(":")
         fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[c] for c in params]

@@ -430,8 +430,7 @@ class HyperpriorVicModel(BaseModel):
             idx = vq_indices.to(real_images.device).long()
             zq = self.vq_indices_to_latent(idx)
             if want_feat:
-                _, _, feat = ops.vq_argmin(zq, self.vq_model.quantize.embedding.weight, want_zq=False, want_feat=True)
-                return zq, idx, feat
+                return zq, idx, self._index_feat(zq, idx)
             return zq, idx
         N, _, H, W = real_images.shape
         _z = self._vq_encode_split(real_images) if max(H, W) > SPLIT_DECODE_RESOLUTION else self.vq_model.encode(real_images)
@@ -444,6 +443,13 @@ class HyperpriorVicModel(BaseModel):
         zq, _, (_, _, idx) = r
         return zq, idx
 
+    def _index_feat(self, latent: Tensor, indices: Tensor) -> Tensor:
+        """cat[latent, one_hot(indices)] from the indices GIVEN (hyperprior_vic_model.py:268-271), not from a search of the gathered
+        latent: the search returns the first of two equal codebook rows, whatever index the caller holds.  Off the hot path."""
+        n_e = self.vq_model.quantize.embedding.weight.shape[0]
+        onehot = torch.nn.functional.one_hot(indices.long(), n_e).permute(0, 3, 1, 2).to(latent.dtype)
+        return torch.cat([latent, onehot], dim=1).contiguous()
+
     def vq_indices_to_latent(self, indices: Tensor) -> Tensor:
         e = self.vq_model.quantize.embedding(indices)          # [N, H, W, D]
         return e.permute(0, 3, 1, 2).contiguous()
@@ -452,7 +458,7 @@ class HyperpriorVicModel(BaseModel):
     def comp_encode(self, real_images: Tensor, gt_vq_latent: Tensor, gt_vq_indices: Tensor, enc_kwargs: Dict = {},
                     feat: Optional[Tensor] = None) -> Tensor:
         if feat is None:
-            _, _, feat = ops.vq_argmin(gt_vq_latent.contiguous(), self.vq_model.quantize.embedding.weight, want_zq=False, want_feat=True)
+            feat = self._index_feat(gt_vq_latent, gt_vq_indices.to(gt_vq_latent.device))
         return self.encoder(real_images, feat, **enc_kwargs)
 
     # ------------------------------------------------------------------ decode (276-288, 413-473)

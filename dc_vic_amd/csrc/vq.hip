@@ -12,6 +12,7 @@
 // LDS and read as wave-uniform broadcasts; each lane owns one latent vector and scans the codes.
 // Roofline: 16 B read + 8 B index (+16 B z_q, + (D+n_e)*4 B one-hot feature when requested) per vector.
 #include "common.h"
+#include "dcvic_vq.h"
 
 #define VQ_MAXD 8
 
@@ -287,8 +288,12 @@ __global__ __launch_bounds__(256) void vq_shard_mfma_kernel(const float* __restr
     }
 }
 
+static thread_local int g_vq_last_variant = DCVIC_VQ_NONE;   // the kernel this thread's last dcvic_vq_argmin_f32 launched (include/dcvic_vq.h)
+extern "C" int dcvic_vq_last_variant(void) { return g_vq_last_variant; }
+
 extern "C" int dcvic_vq_argmin_f32(const float* z, const float* codebook, int64_t* idx, float* zq, float* feat, int N, int D,
                                    int HW, int n_e, void* stream) {
+    g_vq_last_variant = DCVIC_VQ_NONE;
     DCVIC_CHECK_ARG(z && codebook && idx && N > 0 && HW > 0 && n_e > 0, "vq_argmin: bad argument");
     DCVIC_CHECK_ARG(D == 4 || D == 8, "vq_argmin: embed_dim %d unsupported (4 or 8)", D);
     DCVIC_CHECK_ARG(N <= 65535, "vq_argmin: batch too large");
@@ -298,6 +303,7 @@ extern "C" int dcvic_vq_argmin_f32(const float* z, const float* codebook, int64_
     const bool shard_ok = D == 4 && n_e % VQS == 0 && ((uintptr_t)codebook % 16) == 0;
     if (shard_ok && (n_e > 1024 || (force && force[0] == 's' && force[1] == 'h'))) {
         dim3 grids(dcvic_cdiv(HW, 256), N);
+        g_vq_last_variant = DCVIC_VQ_SHARD;
         vq_shard_mfma_kernel<<<grids, 256, 0, (hipStream_t)stream>>>(z, codebook, idx, zq, feat, HW, n_e);
         DCVIC_CHECK_LAUNCH("vq_argmin(shard)");
         return DCVIC_OK;
@@ -310,17 +316,21 @@ extern "C" int dcvic_vq_argmin_f32(const float* z, const float* codebook, int64_
         const bool big = (long long)N * dcvic_cdiv(HW, 1024) >= 2048;
         if (big) {
             dim3 grid4(dcvic_cdiv(HW, 1024), N);
+            g_vq_last_variant = DCVIC_VQ_PACKED2;
             vq_argmin4_kernel<2><<<grid4, 256, (size_t)n_e * sizeof(float), (hipStream_t)stream>>>(z, codebook, idx, zq, feat, HW, n_e);
         } else {
             dim3 grid4(dcvic_cdiv(HW, 512), N);
+            g_vq_last_variant = DCVIC_VQ_PACKED1;
             vq_argmin4_kernel<1><<<grid4, 256, (size_t)n_e * sizeof(float), (hipStream_t)stream>>>(z, codebook, idx, zq, feat, HW, n_e);
         }
     } else if (D == 4) {
         static std::atomic<unsigned> m4{0};
+        g_vq_last_variant = DCVIC_VQ_LDS4;
         if (DcvicAttrOnce once_{m4}) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(vq_argmin_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         vq_argmin_kernel<4><<<grid, 256, lds, (hipStream_t)stream>>>(z, codebook, idx, zq, feat, HW, n_e);
     } else {
         static std::atomic<unsigned> m8{0};
+        g_vq_last_variant = DCVIC_VQ_LDS8;
         if (DcvicAttrOnce once_{m8}) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(vq_argmin_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         vq_argmin_kernel<8><<<grid, 256, lds, (hipStream_t)stream>>>(z, codebook, idx, zq, feat, HW, n_e);
     }

@@ -322,7 +322,7 @@ def test_vq_argmin_index_exact(dev, synth_sd):
     for seed, scale, shape, n_e in ((41, 1.0, (2, 4, 64, 64), 256), (42, 0.01, (3, 4, 24, 40), 256),
                                     (43, 3.0, (1, 4, 7, 5), 256), (49, 0.02, (2, 4, 33, 31), 255),
                                     (50, 0.01, (1, 4, 16, 40), 1)):
-        cb = cb_full[:n_e].contiguous()       # odd sizes exercise the packed kernel's padding code
+        cb = cb_full[:n_e].contiguous()       # n_e = 255 and 1 are no multiple of 8: they go to the generic LDS kernel, 256 to the packed one
         z = rnd(*shape, seed=seed, scale=scale)
         zq_ref, idx_ref = O.vq_quantize({"vq_model.quantize.embedding.weight": cb}, z)
         idx, zq, feat = ops.vq_argmin(z.to(dev), cb.to(dev), want_zq=True, want_feat=True)

@@ -15,148 +15,23 @@
 // them in wave order, so all 16 waves hold the same bits.  Per-workgroup fp64 partials go to the workspace; a one-workgroup pass
 // adds them in a fixed order.  No atomics: the same inputs give the same bits on every run.
 //
-// The kernel is one template; its OASIS flag selects the three places where the two losses differ:
+// The kernel (csrc/chan_ce_core.h, shared with csrc/sample_loss.hip) is one template; its OASIS flag selects the three places where the two losses differ:
 //   1. the effective class: OASIS `is_real ? target + 1, valid in [1, C) : 0` (target may be null when fake); focal `target`,
 //      valid in [0, C);
 //   2. OASIS also sums each thread's logits of class >= 1 in fp64 (the logged score): a second double per workgroup partial;
 //   3. the per-position value f and the factor A on (p_j - [j == t]): OASIS f = ce, A = 1; focal f = q^gamma * ce,
 //      A = q^gamma + gamma * q^(gamma-1) * p_t * ce, formed in fp64 from ce: q = -expm1(-ce) keeps its digits as p_t -> 1, where
 //      1 - exp(-ce) has none.  At gamma = 0 focal is f = ce, A = 1 and gives the bits of OASIS on the shifted classes.
-#include "common.h"
+#include "chan_ce_core.h"
 #include "dcvic_loss.h"
 
 namespace {
 
-constexpr int WAVES = 16, KREG = 17, POS = 64;
-
-__device__ __forceinline__ double wsum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// is_real is read by the OASIS instantiation only, gamma by the focal one only
-template <bool CACHED, bool OASIS>
-__global__ __launch_bounds__(WAVES * 64) void chan_ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                             float* __restrict__ dlogits, double* __restrict__ part, int C, int HW, int tiles,
-                                                             int is_real, double gamma, float scale) {
-    __shared__ float s_m[WAVES][POS], s_s[WAVES][POS];
-    __shared__ float s_t[POS];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int n = blockIdx.x / tiles, p = (blockIdx.x % tiles) * POS + lane;
-    const bool active = p < HW;
-    const float* lp = logits + (long long)n * C * HW + p;
-    // effective class; -1 marks one outside the valid range (the loss becomes NaN, nothing is indexed by it)
-    constexpr int SHIFT = OASIS ? 1 : 0;
-    int t = 0;
-    if (active && (!OASIS || is_real)) {
-        const long long tt = (long long)target[(long long)n * HW + p] + SHIFT;
-        t = (tt >= SHIFT && tt < C) ? (int)tt : -1;
-    }
-    if (w == 0 && t < 0) s_t[lane] = __builtin_nanf("");
-
-    float v[KREG];
-    float m = -INFINITY, s = 0.f;
-    double sc = 0.0;                                   // OASIS: sum of this thread's logits of class >= 1
-    if (CACHED) {
-#pragma unroll
-        for (int k = 0; k < KREG; ++k) {
-            const int c = w + WAVES * k;
-            v[k] = (active && c < C) ? lp[(long long)c * HW] : -INFINITY;
-        }
-#pragma unroll
-        for (int k = 0; k < KREG; ++k) m = fmaxf(m, v[k]);
-#pragma unroll
-        for (int k = 0; k < KREG; ++k) {
-            const int c = w + WAVES * k;
-            if (active && c < C) {
-                s += expf(v[k] - m);
-                if (OASIS && c >= 1) sc += (double)v[k];
-                if (c == t) s_t[lane] = v[k];
-            }
-        }
-    } else if (active) {
-        for (int c0 = w; c0 < C; c0 += 4 * WAVES) {
-            float x[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int c = c0 + WAVES * j;
-                x[j] = c < C ? lp[(long long)c * HW] : -INFINITY;
-            }
-            const float mx = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
-            if (mx > m) {
-                s *= expf(m - mx);                     // (first round: s = 0 and expf(-inf) = 0)
-                m = mx;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int c = c0 + WAVES * j;
-                if (c < C) {
-                    s += expf(x[j] - m);
-                    if (OASIS && c >= 1) sc += (double)x[j];
-                    if (c == t) s_t[lane] = x[j];
-                }
-            }
-        }
-    }
-    s_m[w][lane] = m;
-    s_s[w][lane] = s;
-    __syncthreads();
-
-    double f_p = 0.0;
-    if (active) {
-        float M = -INFINITY, S = 0.f;
-#pragma unroll
-        for (int i = 0; i < WAVES; ++i) M = fmaxf(M, s_m[i][lane]);
-#pragma unroll
-        for (int i = 0; i < WAVES; ++i) S += s_s[i][lane] * expf(s_m[i][lane] - M);     // a wave without channels: 0 * expf(-inf) = 0
-        // S >= 1 and M >= z_t, so ce >= 0 and q stays in [0, 1]
-        const double ce = (double)logf(S) + ((double)M - (double)s_t[lane]);
-        double A = 1.0;                                // d f / d ce, the factor on (p_j - [j == t])
-        f_p = ce;
-        if constexpr (!OASIS) {
-            if (gamma != 0.0) {
-                const double pt = exp(-ce), q = -expm1(-ce);
-                const double qg1 = pow(q, gamma - 1.0);    // gamma >= 1: pow(0, 0) = 1, pow(0, > 0) = 0, never Inf
-                const double qg = qg1 * q;
-                f_p = qg * ce;
-                A = qg + gamma * qg1 * pt * ce;
-            }
-        }
-        if (dlogits) {
-            float* dp = dlogits + (long long)n * C * HW + p;
-            const float inv = 1.f / S, coef = scale * (float)A;     // OASIS: scale * 1.f is scale
-            if (CACHED) {
-#pragma unroll
-                for (int k = 0; k < KREG; ++k) {
-                    const int c = w + WAVES * k;
-                    if (c < C) dp[(long long)c * HW] = coef * (expf(v[k] - M) * inv - (c == t ? 1.f : 0.f));
-                }
-            } else {
-                for (int c = w; c < C; c += WAVES)
-                    dp[(long long)c * HW] = coef * (expf(lp[(long long)c * HW] - M) * inv - (c == t ? 1.f : 0.f));
-            }
-        }
-    }
-    // workgroup partials: the value from wave 0 (every wave holds the same values); OASIS: the class >= 1 sum over the waves in order
-    constexpr int STRIDE = OASIS ? 2 : 1;
-    if (w == 0) {
-        const double L = wsum_d(f_p);
-        if (lane == 0) part[STRIDE * (long long)blockIdx.x] = L;
-    }
-    if constexpr (OASIS) {
-        __shared__ double s_red[WAVES];
-        const double Q = wsum_d(sc);
-        if (lane == 0) s_red[w] = Q;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double q = 0.0;
-#pragma unroll
-            for (int i = 0; i < WAVES; ++i) q += s_red[i];
-            part[2 * (long long)blockIdx.x + 1] = q;
-        }
-    }
-}
+using chan_ce::KREG;
+using chan_ce::POS;
+using chan_ce::WAVES;
+using chan_ce::chan_ce_kernel;
+using chan_ce::wsum_d;
 
 // one workgroup: thread i adds the partials i, i + 256, ... in ascending order, then the 256 sums are added lane-tree by wave.
 // OASIS: two doubles per workgroup partial, the second is the class >= 1 sum behind `score` (which may be null)
@@ -184,21 +59,16 @@ __global__ __launch_bounds__(256) void chan_ce_final_kernel(const double* __rest
     }
 }
 
-long long chan_ce_blocks(int N, int HW) {
-    if (N <= 0 || HW <= 0) return 0;
-    return (long long)N * dcvic_cdiv(HW, POS);
-}
-
 // the size check and the launches, after the entry point's own argument checks
 template <bool OASIS>
 int chan_ce_launch(const float* logits, const int64_t* target, int is_real, double gamma, double scale, float* loss, float* dlogits, float* score,
                    double* workspace, int N, int C, int HW, hipStream_t stream) {
     constexpr const char* name = OASIS ? "oasis_ce" : "focal_ce";
-    const long long blocks = chan_ce_blocks(N, HW);
-    DCVIC_CHECK_ARG(blocks <= 0x3fffffff && (long long)C * HW <= 0x7fffffffLL, "%s: N=%d C=%d HW=%d too large", name, N, C, HW);
+    const long long blocks = chan_ce::blocks(N, HW);
+    DCVIC_CHECK_ARG(chan_ce::fits(N, C, HW), "%s: N=%d C=%d HW=%d too large", name, N, C, HW);
     const int tiles = dcvic_cdiv(HW, POS);
     auto kernel = C <= KREG * WAVES ? chan_ce_kernel<true, OASIS> : chan_ce_kernel<false, OASIS>;
-    kernel<<<(unsigned)blocks, WAVES * 64, 0, stream>>>(logits, target, dlogits, workspace, C, HW, tiles, is_real, gamma, (float)scale);
+    kernel<<<(unsigned)blocks, WAVES * 64, 0, stream>>>(logits, target, dlogits, workspace, C, HW, tiles, is_real, gamma, (float)scale, nullptr);
     DCVIC_CHECK_LAUNCH(name);
     chan_ce_final_kernel<OASIS><<<1, 256, 0, stream>>>(workspace, (int)blocks, scale, 1.0 / ((double)N * (double)(C - 1) * (double)HW), loss, score);
     DCVIC_CHECK_LAUNCH(OASIS ? "oasis_ce_final" : "focal_ce_final");
@@ -207,9 +77,9 @@ int chan_ce_launch(const float* logits, const int64_t* target, int is_real, doub
 
 }  // namespace
 
-extern "C" long long dcvic_oasis_ce_workspace_doubles(int N, int HW) { return 2 * chan_ce_blocks(N, HW); }
+extern "C" long long dcvic_oasis_ce_workspace_doubles(int N, int HW) { return 2 * chan_ce::blocks(N, HW); }
 
-extern "C" long long dcvic_focal_ce_workspace_doubles(int N, int HW) { return chan_ce_blocks(N, HW); }
+extern "C" long long dcvic_focal_ce_workspace_doubles(int N, int HW) { return chan_ce::blocks(N, HW); }
 
 extern "C" int dcvic_oasis_ce_f32(const float* logits, const int64_t* target, int is_real, double scale, float* loss, float* dlogits,
                                   float* score, double* workspace, int N, int C, int HW, void* stream) {

@@ -41,11 +41,15 @@ def const(t: Tensor) -> Var:
 class ParamGroup:
     """The trainable parameters of some modules as views of ONE flat fp32 buffer (+ flat grad / Adam moments)."""
 
-    def __init__(self, modules: Sequence[nn.Module], device):
+    def __init__(self, modules: Sequence[nn.Module], device, select: Optional[Callable[[str], bool]] = None):
+        """`select` (optional): called with a parameter's name within its module (as named_parameters gives it); only the parameters it
+        accepts join the group.  The others keep their own storage and receive no gradient from a Ctx of this group."""
         self.params: List[nn.Parameter] = []
         seen = set()
         for m in modules:
-            for p in m.parameters():
+            for name, p in m.named_parameters():
+                if select is not None and not select(name):
+                    continue
                 if id(p) not in seen and p.dtype == torch.float32:
                     seen.add(id(p))
                     self.params.append(p)
@@ -512,6 +516,25 @@ def focal_cross_entropy_loss(ctx: Ctx, logits: Var, target: Tensor, weight: floa
     val, dl = K.focal_ce(ld, target.contiguous(), gamma, weight / (N * H * W) if reduction == "mean" else weight, want_grad=logits.needs_grad)
     if dl is not None:
         acc(logits, dl)
+    return val
+
+
+def focal_cross_entropy_loss_weighted(ctx: Ctx, logits: Var, target: Tensor, w: Tensor, gamma: float) -> Tensor:
+    """sum_n w[n] * sum_positions (1 - p_t)^gamma * CrossEntropy of image n (logits [N, C, H, W], target [N, H, W], w a device fp32 [N]
+    vector: losses.sample_loss_weights states apply_loss_weight of the rate-distortion trainers in this form): value and gradient from
+    one pass of csrc/sample_loss.hip; the gradient is seeded into `logits`."""
+    val, dl, _ = K.focal_ce_sample(_dense(logits.data), target.contiguous(), w, gamma, want_grad=logits.needs_grad)
+    if dl is not None:
+        acc(logits, dl)
+    return val
+
+
+def mse_loss_weighted(ctx: Ctx, a: Var, target: Tensor, w: Tensor) -> Tensor:
+    """sum_n w[n] * sum((a[n] - target[n])^2) with w a device fp32 [N] vector (losses.sample_loss_weights): value and gradient from
+    one pass of csrc/sample_loss.hip over `a` (which may be a channel-slice view); the gradient is seeded into `a`."""
+    val, da, _ = K.sq_err_sample(a.data, target.contiguous(), w, want_grad=a.needs_grad)
+    if da is not None:
+        acc(a, da)
     return val
 
 

@@ -1,5 +1,5 @@
-"""ctypes wrappers of the training-step kernels (csrc/train.hip, include/dcvic.h "Training step"; csrc/chan_ce.hip; csrc/rate_train.hip,
-include/dcvic_rate.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
+"""ctypes wrappers of the training-step kernels (csrc/train.hip, include/dcvic.h "Training step"; csrc/chan_ce.hip; csrc/sample_loss.hip,
+include/dcvic_sample_loss.h; csrc/rate_train.hip, include/dcvic_rate.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
 from __future__ import annotations
 
 import ctypes
@@ -194,6 +194,36 @@ def focal_ce(logits: Tensor, target: Tensor, gamma: float, scale: float, want_gr
     N, Cc, HW, ws, loss, dl = _chan_ce_buffers("focal_ce", lib().dcvic_focal_ce_workspace_doubles, logits, target, want_grad)
     check(lib().dcvic_focal_ce_f32(_p(logits), _p(target), float(gamma), scale, _p(loss), _p(dl), _p(ws), N, Cc, HW, _stream()), "focal_ce")
     return loss, dl
+
+
+# ------------------------------------------------------------------------------------------- per-image weights (csrc/sample_loss.hip)
+def focal_ce_sample(logits: Tensor, target: Tensor, w: Tensor, gamma: float, want_grad: bool = True, want_per_sample: bool = False):
+    """Focal cross entropy with one weight per image in one pass over logits [N, C, H, W]: (loss, dlogits or None, per_sample or None)
+    with S[n] = sum_positions (1 - p_t)^gamma * CE of image n, loss = sum_n w[n] * S[n], dlogits its gradient and per_sample = S."""
+    N, Cc, HW, ws, loss, dl = _chan_ce_buffers("focal_ce_sample", lib().dcvic_focal_ce_sample_workspace_doubles, logits, target, want_grad)
+    per = torch.empty(N, dtype=torch.float32, device=logits.device) if want_per_sample else None
+    check(lib().dcvic_focal_ce_sample_f32(_p(logits), _p(target), _p(_flat_f32(w, N, "focal_ce_sample: sample weights")), float(gamma), _p(loss),
+                                          _p(dl), _p(per), _p(ws), N, Cc, HW, _stream()), "focal_ce_sample")
+    return loss, dl, per
+
+
+def sq_err_sample(a: Tensor, b: Tensor, w: Tensor, want_grad: bool = True, want_per_sample: bool = False):
+    """Squared error with one weight per image, value and gradient in one pass: (loss, da or None, per_sample or None) with
+    S[n] = sum (a[n] - b[n])^2, loss = sum_n w[n] * S[n] and da = 2 w[n] (a - b).  `a` [N, ...] is dense within an image and may have
+    its own batch stride (a channel-slice view); `b` is contiguous."""
+    N = a.shape[0]
+    M = a.numel() // max(N, 1)
+    if a.dtype != torch.float32 or not a.is_cuda or a.dim() < 2 or (N > 0 and not a[0].is_contiguous()):
+        raise ValueError(f"sq_err_sample: a must be an fp32 device tensor [N, ...] that is dense within an image, got {a.dtype} {tuple(a.shape)}")
+    if b.dtype != torch.float32 or b.shape != a.shape or not b.is_contiguous() or b.device != a.device:
+        raise ValueError(f"sq_err_sample: b must be a contiguous fp32 tensor {tuple(a.shape)}, got {b.dtype} {tuple(b.shape)}")
+    ws = _workspace(int(lib().dcvic_sq_err_sample_workspace_doubles(N, M)), a.device, "sq_err_sample", torch.float64)
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    da = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_grad else None
+    per = torch.empty(N, dtype=torch.float32, device=a.device) if want_per_sample else None
+    check(lib().dcvic_sq_err_sample_f32(_p(a), a.stride(0) if N > 1 else M, _p(b), _p(_flat_f32(w, N, "sq_err_sample: sample weights")), _p(loss),
+                                        _p(da), _p(per), _p(ws), N, M, _stream()), "sq_err_sample")
+    return loss, da, per
 
 
 # ------------------------------------------------------------------------------------------- the rate term (csrc/rate_train.hip)

@@ -42,8 +42,9 @@ class CrossEntropyLoss:
 @LOSS_REGISTRY.register()
 class FocalCrossEntropyLoss:
     """cross_entropy_loss.py:32-53: loss_weight * reduce((1 - p_t)^gamma * CE) with reduction mean or sum, one pass of csrc/chan_ce.hip.
-    `reduction: none` returns a per-position map for the per-sample beta weighting of the rate-distortion trainers, which are not
-    built; the reference forwards further keywords to nn.CrossEntropyLoss, none of which is built either."""
+    `reduction: none` returns a per-position map for the per-sample beta weighting of the rate-distortion trainers: this class, which
+    returns one value, refuses it -- train/rd_trainer.py forms that loss with A.focal_cross_entropy_loss_weighted and
+    sample_loss_weights below.  The reference forwards further keywords to nn.CrossEntropyLoss, none of which is built."""
 
     def __init__(self, loss_weight: float, gamma: float, reduction: str = "mean", **kwargs):
         if kwargs:
@@ -91,10 +92,35 @@ class RateLoss:
         return w.to(torch.float32).contiguous()
 
 
+def sample_loss_weights(loss_weight: float, reduction: str, N: int, elems_per_image: int, beta_weight: Tensor, device=None) -> Tensor:
+    """The fp32 [N] vector w with sum_n w[n] * S[n] equal to apply_loss_weight(code_loss(...), beta_weight) of
+    DualBetaCondRateDistortionVqCodeTrainer (dual_cond_rate_distortion_vq_code_trainer.py:92-98,189-198), where S[n] is image n's own
+    sum of the per-element terms (focal cross entropy per position, squared error per element: A.focal_cross_entropy_loss_weighted,
+    A.mse_loss_weighted) and the code loss carries `loss_weight` and `reduction` (cross_entropy_loss.py:32-53, distortion_loss.py:43-51):
+      none: the map's mean over every axis but the batch, then (loss * beta_weight).mean():  w[n] = loss_weight * beta_weight[n] / (N * elems)
+      mean: the scalar times mean(beta_weight):                                              w[n] = loss_weight * mean(beta_weight) / (N * elems)
+      sum:                                                                                   w[n] = loss_weight * mean(beta_weight)
+    beta_weight is exp(beta_vq) or beta_vq + offset, of length N or -- sample_beta_batch: false -- 1, which broadcasts.  Formed in fp64,
+    rounded once."""
+    import torch
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"reduction: {reduction} is unknown; use mean, sum or none")
+    if N <= 0 or elems_per_image <= 0:
+        raise ValueError(f"sample_loss_weights: N={N} images of {elems_per_image} elements")
+    if beta_weight.dim() != 1 or beta_weight.numel() not in (1, N):
+        raise ValueError(f"beta_weight: a vector of {N} per-sample weights (or of 1, which broadcasts), got {tuple(beta_weight.shape)}")
+    b = beta_weight.to(device=device if device is not None else beta_weight.device, dtype=torch.float64)
+    if reduction == "none":
+        w = (b * (float(loss_weight) / (N * elems_per_image))).expand(N)
+    else:
+        w = (b.mean() * (float(loss_weight) / (N * elems_per_image if reduction == "mean" else 1))).expand(N)
+    return w.to(torch.float32).contiguous()
+
+
 # ---------------------------------------------------------------------------------------------------- the YAML's `loss` section
-# the reference's trainers with a rate term and per-sample beta weights (config/exp1_stage1_1.yaml, exp1_stage1_2.yaml): not built,
-# scripts/train.py refuses them by `trainer.type`.  Their `rate_loss` entry and `reduction: none` are those trainers' business and
-# are passed over here; in a GAN-stage config both are refused.
+# the reference's trainers with a rate term and per-sample beta weights (config/exp1_stage1_1.yaml, exp1_stage1_2.yaml): the second is
+# train/rd_trainer.py, the first is not built and scripts/train.py refuses it by `trainer.type`.  Their `rate_loss` entry and
+# `reduction: none` are read for them here; in a GAN-stage config both are refused.
 RATE_DISTORTION_TRAINERS = ("RateDistortionVqCodeTrainer", "DualBetaCondRateDistortionVqCodeTrainer")
 _ENTRIES = ("distortion_loss", "perceptual_loss", "gan_loss", "code_distortion_loss", "code_ce_loss", "rate_loss")
 _WEIGHT_NAME = {"distortion_loss": "distortion", "perceptual_loss": "perceptual", "gan_loss": "gan", "code_distortion_loss": "code_distortion",
@@ -128,6 +154,7 @@ def read_loss_section(opt) -> Dict[str, Any]:
       code_distortion_reduction  'mean' or 'sum'
       per_sample           True when `trainer.type` names a rate-distortion trainer (its `reduction: none` entries are kept as read)
       line                 the `[train] losses:` log text
+      rate                 under a rate-distortion trainer dict(loss_weight or None, reduction) of `rate_loss`, else None
     `gan_loss` is judged by scripts/train.py's choose_gan_trainer; only its weight is read here."""
     try:
         loss = opt["loss"]
@@ -165,6 +192,20 @@ def read_loss_section(opt) -> Dict[str, Any]:
     # rate_loss: no GAN-stage trainer has a rate term (fix_entropy_models)
     if "rate_loss" in entries and not per_sample:
         _refuse("rate_loss", entries["rate_loss"].get("type", entries["rate_loss"]), "has no place in the GAN-stage trainers: they train no rate term")
+
+    # rate_loss under a rate-distortion trainer: RateLoss(loss_weight, target_rate, reduction)
+    rate = None
+    if per_sample:
+        e = entries.get("rate_loss", {})
+        if e.get("type", "RateLoss") != "RateLoss":
+            _refuse("rate_loss.type", e["type"], "is not built, expected RateLoss")
+        _only(e, "rate_loss", ("type", "loss_weight", "target_rate", "reduction"))
+        rate = dict(loss_weight=e.get("loss_weight"), reduction=reduction_of("rate_loss", e, ("mean", "sum", "none")))
+        if rate["loss_weight"] is not None:
+            try:
+                rate["loss_weight"] = float(rate["loss_weight"])
+            except (TypeError, ValueError):
+                _refuse("rate_loss.loss_weight", rate["loss_weight"], "is not a number")
 
     # code_ce_loss
     e = entries.get("code_ce_loss", {})
@@ -224,7 +265,8 @@ def read_loss_section(opt) -> Dict[str, Any]:
     ce_desc = "CrossEntropyLoss" if code_ce["type"] != "FocalCrossEntropyLoss" else f"FocalCrossEntropyLoss(gamma={code_ce['gamma']:g}, {code_ce['reduction']})"
     line = (f"distortion {d_desc} factor {factor:g}; perceptual LPIPSLoss(net=alex); code_distortion VanillaMSELoss({cd_red}); "
             f"code_ce {ce_desc}")
-    return dict(weights=weights, code_ce=code_ce, distortion_factor=factor, code_distortion_reduction=cd_red, per_sample=per_sample, line=line)
+    return dict(weights=weights, code_ce=code_ce, distortion_factor=factor, code_distortion_reduction=cd_red, per_sample=per_sample, line=line,
+                rate=rate)
 
 
 def build_code_ce_loss(code_ce: Dict[str, Any], loss_weight: float):

@@ -67,10 +67,11 @@ def nlam(ctx: Ctx, m: ChengNLAM, x: Var) -> Var:
     return A.nlam_gate(ctx, x, t, A.conv(ctx, a, m.conv))
 
 
-def decoder_get_feats(ctx: Ctx, dec, y_hat: Tensor, beta_1, beta_2):
-    """ElicDualBetaFtFeatFusionDecoder.get_feats with a tape (y_hat is a constant: the entropy side runs under no_grad)."""
-    cond = cond_vector(ctx, dec, beta_1, beta_2, y_hat.device)
-    x = A.const(y_hat)
+def decoder_get_feats(ctx: Ctx, dec, y_hat, beta_1, beta_2):
+    """ElicDualBetaFtFeatFusionDecoder.get_feats with a tape.  y_hat is a Tensor (a constant: the GAN stages run the entropy side under
+    no_grad) or a Var (estimate_entropy_train's quantized_code.y: the gradient that arrives on it continues into the analysis side)."""
+    x = y_hat if isinstance(y_hat, Var) else A.const(y_hat)
+    cond = cond_vector(ctx, dec, beta_1, beta_2, x.data.device)
     s0, t0 = beta_vectors(ctx, dec.init_fuse, cond)
     x = A.chan_affine(ctx, x, s0, t0, add_x=True)                         # init_fuse(x, c) + x   (:343)
     feats: Dict[str, Var] = {}

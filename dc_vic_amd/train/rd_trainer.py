@@ -1,0 +1,192 @@
+"""Stage 1-2 rate-distortion training step of DC-VIC on the HIP kernels.
+
+Mirrors src/trainer/dual_cond_rate_distortion_vq_code_trainer.py:56-200 (`DualBetaCondRateDistortionVqCodeTrainer`, over
+rate_distortion_vq_code_trainer.py:61-108 and base_model.py:132-146) with config/exp1_stage1_2.yaml: the whole compression model but the
+frozen VQGAN trains with Adam + MultiStepLR on  rate + distortion + perceptual + code_distortion + code_ce, where the rate term and
+the two code losses carry one weight per image, exp(beta) or beta + offset (`apply_loss_weight`); the entropy bottleneck's `quantiles`
+train apart, with their own Adam on EntropyBottleneck.loss(), AFTER the main step (`optimize_aux_parameters`).
+
+The step runs on the tape: nets.analysis_forward (encoder, hyperprior, CHARM, both entropy models with uniform noise; the rate term's
+gradients are seeded by csrc/rate_train.hip), then decoder_get_feats on the `Var` y_hat, the estimator, the argmax LUT and the fusion
+decoder, so the image and code losses reach the analysis side through y_hat's straight-through estimator.  The per-image weighting of the
+code losses is csrc/sample_loss.hip (A.mse_loss_weighted, A.focal_cross_entropy_loss_weighted, losses.sample_loss_weights).
+
+Differences, stated: those of trainer.py (LPIPS weights, data-parallel averaging); the uniform noise comes from a trainer-owned device
+torch.Generator, not from torch's global one; `model.gumbel_sampling: true` is refused."""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .. import ops
+from ..registry import TRAINER_REGISTRY
+from . import autograd as A
+from . import kernels as K
+from . import nets
+from .autograd import Ctx, ParamGroup
+from .losses import RateLoss, check_focal_gamma, sample_loss_weights
+from .trainer import Adam, BetaPairTrainerBase, MultiStepLR, allreduce_mean_, loss_anomaly
+
+Tensor = torch.Tensor
+
+# config/exp1_stage1_2.yaml's loss_weight values
+DEFAULT_RD_LOSS = dict(rate=0.5, distortion=50.0, perceptual=1.0, code_distortion=0.006, code_ce=0.003)
+BETA_POLICIES = ("linear", "exp")
+LOG_KEYS = ("rate", "distortion", "perceptual", "code_distortion", "code_ce", "total", "qbpp", "vq_acc", "lr", "aux")
+
+
+def is_main_parameter(name: str) -> bool:
+    """rate_distortion_vq_code_trainer.py:61-73 / base_model.py:132-146: every parameter of the model except the frozen VQGAN's and the
+    entropy bottleneck's `quantiles` (which the aux optimizer owns)."""
+    return not name.startswith("vq_model.") and not name.endswith(".quantiles")
+
+
+def beta_loss_weights(policy: str, offset: float, beta_vq: Tensor, beta_rate: Tensor) -> Tuple[Tensor, Tensor]:
+    """calc_vq_rate_loss_weight (:71-78) -> (vq_weight, rate_weight), fp32 as the reference's."""
+    if policy == "linear":
+        return beta_vq.float() + offset, beta_rate.float() + offset
+    if policy == "exp":
+        return torch.exp(beta_vq.float()), torch.exp(beta_rate.float())
+    raise ValueError(f"beta_policy: {policy} is unknown, expected linear or exp")
+
+
+@TRAINER_REGISTRY.register()
+class DualBetaCondRateDistortionVqCodeTrainer(BetaPairTrainerBase):
+    def __init__(self, model, lr: float = 1e-4, aux_lr: float = 1e-3, milestones=(300000,), gamma: float = 0.1,
+                 clip_max_norm: Optional[float] = 1.0, loss_weights: Optional[Dict[str, float]] = None, beta_policy: str = "linear",
+                 beta_offset: float = 1.0, sample_beta_batch: bool = False, dist=None, seed: int = 0, lpips_state: Optional[Dict[str, Tensor]] = None,
+                 rate_reduction: str = "mean", code_ce_gamma: float = 0.0, code_ce_reduction: str = "mean", code_distortion_reduction: str = "mean",
+                 distortion_factor: float = 0.25, gumbel_sampling: bool = False):
+        """`loss_weights`: {rate, distortion, perceptual, code_distortion, code_ce} over DEFAULT_RD_LOSS; the three `*_reduction`s are
+        none, mean or sum (RateLoss, FocalCrossEntropyLoss, VanillaMSELoss); `code_ce_gamma` 0 is the plain cross entropy;
+        `beta_policy` / `beta_offset` / `sample_beta_batch` default as the reference's constructor does."""
+        if gumbel_sampling:
+            raise ValueError("model.gumbel_sampling: true is not built (the Gumbel-softmax sampling of the VQ indices in training mode): set it to false")
+        if beta_policy not in BETA_POLICIES:
+            raise ValueError(f"beta_policy: {beta_policy} is unknown, expected linear or exp")
+        for what, r in (("rate", rate_reduction), ("code_ce", code_ce_reduction), ("code_distortion", code_distortion_reduction)):
+            if r not in ("none", "mean", "sum"):
+                raise ValueError(f"{what} reduction: {r} is unknown; use none, mean or sum")
+        self.model = model
+        dev = next(model.decoder.parameters()).device
+        self.device = dev
+        self.group = ParamGroup([model], dev, select=is_main_parameter)
+        self.aux_group = ParamGroup([model.entropy_model_z], dev, select=lambda name: name == "quantiles")
+        self.opt, self.aux_opt = Adam(self.group, lr), Adam(self.aux_group, aux_lr)
+        self.sched = MultiStepLR(lr, list(milestones), gamma)
+        self.clip = clip_max_norm
+        self.w = dict(DEFAULT_RD_LOSS)
+        if loss_weights:
+            self.w.update(loss_weights)
+        self.rate_loss = RateLoss(self.w["rate"], reduction=rate_reduction)
+        self.code_ce_gamma, self.code_ce_reduction = check_focal_gamma(code_ce_gamma), code_ce_reduction
+        self.code_distortion_reduction, self.distortion_factor = code_distortion_reduction, float(distortion_factor)
+        self.beta_policy, self.beta_offset, self.sample_beta_batch = beta_policy, float(beta_offset), bool(sample_beta_batch)
+        self.last_beta_rate: Optional[Tensor] = None
+        self.last_beta_vq: Optional[Tensor] = None
+        self.dist = dist
+        self.rng = np.random.RandomState(seed)                                 # the beta samplers
+        self.noise_gen = torch.Generator(device=dev).manual_seed(seed)         # the entropy models' uniform noise
+        self._build_lpips(self.w["perceptual"], lpips_state, dev)
+
+    # ---------------------------------------------------------------- training state
+    def _tagged(self):
+        return (("main", self.group, self.opt), ("aux", self.aux_group, self.aux_opt))
+
+    def training_state(self, current_iter: int) -> Dict:
+        st = {"iter": int(current_iter), "rng": self.rng.get_state(), "noise_gen": self.noise_gen.get_state().clone(),
+              "last_epoch": int(self.sched.last_epoch)}
+        for tag, grp, opt_ in self._tagged():
+            st[tag] = {"m": grp.m.detach().cpu().clone(), "v": grp.v.detach().cpu().clone(), "t": int(opt_.t), "numel": int(grp.numel())}
+        return st
+
+    def load_training_state(self, st: Dict) -> int:
+        for tag, grp, opt_ in self._tagged():
+            s_ = st[tag]
+            if int(s_["numel"]) != grp.numel():
+                raise ValueError(f"training state: {tag} group has {s_['numel']} parameters, this model {grp.numel()}")
+            grp.m.copy_(s_["m"].to(grp.m.device)); grp.v.copy_(s_["v"].to(grp.v.device))
+            opt_.t = int(s_["t"])
+        self.sched.last_epoch = int(st["last_epoch"])
+        self.rng.set_state(st["rng"])
+        self.noise_gen.set_state(st["noise_gen"])
+        return int(st["iter"])
+
+    def resync_parameters(self) -> None:
+        """After a state dict was loaded into the model: parameters are views of the flat buffers, so load_state_dict's copy_ already
+        wrote them; cached packed weights are stale."""
+        self.group.refresh_plans(); self.aux_group.refresh_plans()
+        self._drop_inference_graphs()
+
+    # ---------------------------------------------------------------- one step
+    def forward_losses(self, ctx: Ctx, real: Tensor, vq_indices: Optional[Tensor], beta_rate: Tensor, beta_vq: Tensor,
+                       noise_y: Optional[Tensor] = None, noise_z: Optional[Tensor] = None):
+        """run_comp_model (:80-90, is_train, fix_entropy_models=False) and calc_g_loss (:153-200) on the tape: every term's gradient is
+        seeded (the rate term's at forward time).  -> (loss terms as 1-element device tensors, outputs)."""
+        m = self.model
+        x = real.to(self.device, dtype=torch.float32).contiguous()
+        N, _, H, W = x.shape
+        vq_w, rate_w = beta_loss_weights(self.beta_policy, self.beta_offset, beta_vq, beta_rate)
+        w_rate = self.rate_loss.sample_weights(N, H * W, rate_w.expand(N).contiguous(), device=self.device)
+        out = nets.analysis_forward(ctx, m, x, beta_rate, beta_vq, vq_indices=vq_indices, noise_y=noise_y, noise_z=noise_z, generator=self.noise_gen,
+                                    weights=w_rate, scale=1.0)
+        feat_1, feats = nets.decoder_get_feats(ctx, m.decoder, out["quantized_code"]["y"], beta_rate, beta_vq)
+        pred_embed, logits = nets.estimator_forward(ctx, m.vq_estimator, feat_1)
+        pq = m.vq_model.post_quant_conv
+        out_idx, lat = ops.argmax_lut(logits.data, m.vq_model.quantize.embedding.weight, pq.weight.reshape(pq.out_channels, -1).contiguous(), pq.bias)
+        fake = nets.fusion_decode(ctx, m.fusion_module, m.vq_model.decoder, A.const(lat), feats, w=1.0)
+        gt_lat, gt_idx = out["gt_vq_latent"], out["gt_vq_indices"]
+        L = {"rate": out["loss"]}
+        L["distortion"] = A.mse_loss(ctx, fake, x, self.w["distortion"] * self.distortion_factor)
+        if self.lpips is not None:
+            from .lpips import lpips_loss
+            L["perceptual"] = lpips_loss(ctx, self.lpips, x, fake, self.w["perceptual"])
+        else:
+            L["perceptual"] = torch.zeros(1, device=self.device)
+        w_cd = sample_loss_weights(self.w["code_distortion"], self.code_distortion_reduction, N, gt_lat[0].numel(), vq_w, device=self.device)
+        L["code_distortion"] = A.mse_loss_weighted(ctx, pred_embed, gt_lat, w_cd)
+        w_ce = sample_loss_weights(self.w["code_ce"], self.code_ce_reduction, N, gt_idx[0].numel(), vq_w, device=self.device)
+        L["code_ce"] = A.focal_cross_entropy_loss_weighted(ctx, logits, gt_idx, w_ce, self.code_ce_gamma)
+        out.update(real=x, fake=fake, pred_embed=pred_embed, logits=logits, out_vq_indices=out_idx,
+                   qbpp=float((out["q_bits_y"].double().sum() + out["q_bits_z"].double().sum()).item()) / (N * H * W))
+        return L, out
+
+    def optimize_aux_parameters(self) -> float:
+        """rate_distortion_vq_code_trainer.py `optimize_aux_parameters`: EntropyBottleneck.loss() on the parameters as they are NOW
+        (after the main step), its gradient w.r.t. `quantiles`, averaged over the ranks, one Adam step."""
+        self.aux_group.zero_grad()
+        aux = A.eb_aux_loss(Ctx([self.aux_group]), self.model.entropy_model_z)
+        allreduce_mean_(self.aux_group.grad, self.dist)
+        self.aux_opt.step()
+        return float(aux.item())
+
+    def optimize_parameters(self, current_iter: int, data_dict: Dict) -> Optional[Dict[str, float]]:
+        real = data_dict["real_images"]
+        n = real.shape[0]
+        beta_rate, beta_vq = data_dict.get("beta_rate"), data_dict.get("beta_vq")
+        if beta_rate is None or beta_vq is None:
+            beta_rate, beta_vq = self.sample_beta_pair(n if self.sample_beta_batch else 1)
+        self.last_beta_rate, self.last_beta_vq = beta_rate, beta_vq
+        self.group.zero_grad()
+        ctx = Ctx([self.group])
+        L, o = self.forward_losses(ctx, real, data_dict.get("vq_indices"), beta_rate, beta_vq, data_dict.get("noise_y"), data_dict.get("noise_z"))
+        log = {k: float(v.item()) for k, v in L.items()}
+        total = sum(log.values())
+        if loss_anomaly(total, self.dist, self.device):  # base_trainer.py:235-245: skip the step -- on EVERY rank or on none
+            ctx.tape = []
+            return None
+        ctx.backward()
+        allreduce_mean_(self.group.grad, self.dist)
+        gscale = None
+        if self.clip:                                   # clip_grad_norm_ over comp_model.parameters(): `quantiles` has no gradient yet
+            gscale = K.clip_scale(K.reduce_loss(K.SUM_SQ, self.group.grad, None, 1.0), self.clip)
+        lr_now = self.sched.lr()
+        self.opt.step(lr_now, gscale)
+        self.sched.step()
+        aux = self.optimize_aux_parameters()
+        self._drop_inference_graphs()
+        vq_acc = float((o["out_vq_indices"] == o["gt_vq_indices"]).float().mean().item())
+        log.update(total=total, qbpp=o["qbpp"], vq_acc=vq_acc, lr=lr_now, aux=aux)
+        return log

@@ -106,40 +106,14 @@ class Adam:
         g.refresh_plans()
 
 
-@TRAINER_REGISTRY.register()
-class DualBetaCondGanDistortionVqCodeTrainer:
-    def __init__(self, model, discriminator, lr_g: float = 1e-4, lr_d: float = 1e-4, milestones=(300000,), gamma: float = 0.1,
-                 clip_max_norm: Optional[float] = 1.0, loss_weights: Optional[Dict[str, float]] = None, sample_beta_batch: bool = True,
-                 dist=None, seed: int = 0, d_milestones=None, d_gamma: Optional[float] = None, lpips_state: Optional[Dict[str, Tensor]] = None,
-                 code_ce_loss=None, distortion_factor: float = 0.25, code_distortion_reduction: str = "mean"):
-        """`code_ce_loss`: a loss object of train/losses.py (CrossEntropyLoss / FocalCrossEntropyLoss, carrying its own weight) or None
-        for CrossEntropyLoss x loss_weights['code_ce']; `distortion_factor`: MSELoss's factor on mean((a - b)^2) of the [-1, 1] images
-        (0.25 = the [0, 1] scale of the shipped configs); `code_distortion_reduction`: VanillaMSELoss's mean or sum."""
-        self.model, self.D = model, discriminator
-        dev = next(model.decoder.parameters()).device
-        self.device = dev
-        # only decoder, vq_estimator, fusion_module are trained (:47-52)
-        self.g_group = ParamGroup([model.decoder, model.vq_estimator, model.fusion_module], dev)
-        self.d_group = ParamGroup([discriminator], dev)
-        self.g_opt, self.d_opt = Adam(self.g_group, lr_g), Adam(self.d_group, lr_d)
-        # config/exp1_stage1_3.yaml:43-60: g_scheduler and d_scheduler are separate YAML entries (same values in the shipped files)
-        self.g_sched = MultiStepLR(lr_g, list(milestones), gamma)
-        self.d_sched = MultiStepLR(lr_d, list(milestones if d_milestones is None else d_milestones), gamma if d_gamma is None else d_gamma)
-        self.clip = clip_max_norm
-        self.w = dict(DEFAULT_LOSS)
-        if loss_weights:
-            self.w.update(loss_weights)
-        if code_distortion_reduction not in ("mean", "sum"):
-            raise ValueError(f"code_distortion_reduction {code_distortion_reduction!r}: expected 'mean' or 'sum'")
-        self.code_ce_loss, self.distortion_factor, self.code_distortion_reduction = code_ce_loss, float(distortion_factor), code_distortion_reduction
-        self.sample_beta_batch = sample_beta_batch
-        self.last_beta_rate: Optional[Tensor] = None   # the pair the last optimize_parameters trained with
-        self.last_beta_vq: Optional[Tensor] = None
-        self.dist = dist
-        self.rng = np.random.RandomState(seed)
-        self.last_fake: Optional[Tensor] = None
+class BetaPairTrainerBase:
+    """What the GAN-stage trainers and the rate-distortion trainer (rd_trainer.py) share: the perceptual network and its weights, the
+    beta-pair samplers (drawing from `self.rng`), validation, and the forgetting of captured inference graphs.  Expects `self.model`,
+    `self.rng` and `self.device`."""
+
+    def _build_lpips(self, weight: float, lpips_state: Optional[Dict[str, Tensor]], dev) -> None:
         self.lpips = None
-        if self.w["perceptual"] > 0:
+        if weight > 0:
             from .lpips import LPIPSAlex
             self.lpips = LPIPSAlex(seed=0).to(dev)
             self.lpips_is_synthetic = lpips_state is None
@@ -160,37 +134,12 @@ class DualBetaCondGanDistortionVqCodeTrainer:
         invalidate_weight_caches(self.lpips)
         self.lpips_is_synthetic = False
 
-    # ---------------------------------------------------------------- training state (base_trainer.py:178-214 saves optimizer + scheduler state)
-    def training_state(self, current_iter: int) -> Dict:
-        st = {"iter": int(current_iter), "rng": self.rng.get_state()}
-        for tag, grp, opt_, sch in (("g", self.g_group, self.g_opt, self.g_sched), ("d", self.d_group, self.d_opt, self.d_sched)):
-            st[tag] = {"m": grp.m.detach().cpu().clone(), "v": grp.v.detach().cpu().clone(), "t": int(opt_.t), "last_epoch": int(sch.last_epoch),
-                       "numel": int(grp.numel())}
-        return st
-
-    def load_training_state(self, st: Dict) -> int:
-        for tag, grp, opt_, sch in (("g", self.g_group, self.g_opt, self.g_sched), ("d", self.d_group, self.d_opt, self.d_sched)):
-            s_ = st[tag]
-            if int(s_["numel"]) != grp.numel():
-                raise ValueError(f"training state: {tag} group has {s_['numel']} parameters, this model {grp.numel()}")
-            grp.m.copy_(s_["m"].to(grp.m.device)); grp.v.copy_(s_["v"].to(grp.v.device))
-            opt_.t, sch.last_epoch = int(s_["t"]), int(s_["last_epoch"])
-        if "rng" in st:
-            self.rng.set_state(st["rng"])
-        return int(st["iter"])
-
     def _drop_inference_graphs(self) -> None:
         """The generator's weights moved in place: hipGraphs captured by compress_batch / decompress_batch before that replay the old
         packed weights -- forget them (the next inference call re-captures)."""
         g = getattr(self.model, "_graphs", None)
         if g is not None:
             g.clear()
-
-    def resync_parameters(self) -> None:
-        """After a state dict was loaded into the modules: parameters are views of the flat buffers, so load_state_dict's copy_
-        already wrote them; cached packed weights are stale."""
-        self.g_group.refresh_plans(); self.d_group.refresh_plans()
-        self._drop_inference_graphs()
 
     # dual_cond_rate_distortion_vq_code_trainer.py:202-233 (_validation)
     def validation_beta_pairs(self) -> List[Tuple[float, float, str]]:
@@ -226,6 +175,66 @@ class DualBetaCondGanDistortionVqCodeTrainer:
         beta_rate = sample_beta_grid(self.rng, m.max_beta_rate, m.num_beta_levels, n)
         beta_vq = sample_beta_grid(self.rng, m.max_beta_vq, m.num_beta_levels, n)
         return beta_rate, beta_vq
+
+
+@TRAINER_REGISTRY.register()
+class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
+    def __init__(self, model, discriminator, lr_g: float = 1e-4, lr_d: float = 1e-4, milestones=(300000,), gamma: float = 0.1,
+                 clip_max_norm: Optional[float] = 1.0, loss_weights: Optional[Dict[str, float]] = None, sample_beta_batch: bool = True,
+                 dist=None, seed: int = 0, d_milestones=None, d_gamma: Optional[float] = None, lpips_state: Optional[Dict[str, Tensor]] = None,
+                 code_ce_loss=None, distortion_factor: float = 0.25, code_distortion_reduction: str = "mean"):
+        """`code_ce_loss`: a loss object of train/losses.py (CrossEntropyLoss / FocalCrossEntropyLoss, carrying its own weight) or None
+        for CrossEntropyLoss x loss_weights['code_ce']; `distortion_factor`: MSELoss's factor on mean((a - b)^2) of the [-1, 1] images
+        (0.25 = the [0, 1] scale of the shipped configs); `code_distortion_reduction`: VanillaMSELoss's mean or sum."""
+        self.model, self.D = model, discriminator
+        dev = next(model.decoder.parameters()).device
+        self.device = dev
+        # only decoder, vq_estimator, fusion_module are trained (:47-52)
+        self.g_group = ParamGroup([model.decoder, model.vq_estimator, model.fusion_module], dev)
+        self.d_group = ParamGroup([discriminator], dev)
+        self.g_opt, self.d_opt = Adam(self.g_group, lr_g), Adam(self.d_group, lr_d)
+        # config/exp1_stage1_3.yaml:43-60: g_scheduler and d_scheduler are separate YAML entries (same values in the shipped files)
+        self.g_sched = MultiStepLR(lr_g, list(milestones), gamma)
+        self.d_sched = MultiStepLR(lr_d, list(milestones if d_milestones is None else d_milestones), gamma if d_gamma is None else d_gamma)
+        self.clip = clip_max_norm
+        self.w = dict(DEFAULT_LOSS)
+        if loss_weights:
+            self.w.update(loss_weights)
+        if code_distortion_reduction not in ("mean", "sum"):
+            raise ValueError(f"code_distortion_reduction {code_distortion_reduction!r}: expected 'mean' or 'sum'")
+        self.code_ce_loss, self.distortion_factor, self.code_distortion_reduction = code_ce_loss, float(distortion_factor), code_distortion_reduction
+        self.sample_beta_batch = sample_beta_batch
+        self.last_beta_rate: Optional[Tensor] = None   # the pair the last optimize_parameters trained with
+        self.last_beta_vq: Optional[Tensor] = None
+        self.dist = dist
+        self.rng = np.random.RandomState(seed)
+        self.last_fake: Optional[Tensor] = None
+        self._build_lpips(self.w["perceptual"], lpips_state, dev)
+
+    # ---------------------------------------------------------------- training state (base_trainer.py:178-214 saves optimizer + scheduler state)
+    def training_state(self, current_iter: int) -> Dict:
+        st = {"iter": int(current_iter), "rng": self.rng.get_state()}
+        for tag, grp, opt_, sch in (("g", self.g_group, self.g_opt, self.g_sched), ("d", self.d_group, self.d_opt, self.d_sched)):
+            st[tag] = {"m": grp.m.detach().cpu().clone(), "v": grp.v.detach().cpu().clone(), "t": int(opt_.t), "last_epoch": int(sch.last_epoch),
+                       "numel": int(grp.numel())}
+        return st
+
+    def load_training_state(self, st: Dict) -> int:
+        for tag, grp, opt_, sch in (("g", self.g_group, self.g_opt, self.g_sched), ("d", self.d_group, self.d_opt, self.d_sched)):
+            s_ = st[tag]
+            if int(s_["numel"]) != grp.numel():
+                raise ValueError(f"training state: {tag} group has {s_['numel']} parameters, this model {grp.numel()}")
+            grp.m.copy_(s_["m"].to(grp.m.device)); grp.v.copy_(s_["v"].to(grp.v.device))
+            opt_.t, sch.last_epoch = int(s_["t"]), int(s_["last_epoch"])
+        if "rng" in st:
+            self.rng.set_state(st["rng"])
+        return int(st["iter"])
+
+    def resync_parameters(self) -> None:
+        """After a state dict was loaded into the modules: parameters are views of the flat buffers, so load_state_dict's copy_
+        already wrote them; cached packed weights are stale."""
+        self.g_group.refresh_plans(); self.d_group.refresh_plans()
+        self._drop_inference_graphs()
 
     @torch.no_grad()
     def generator_forward(self, ctx: Ctx, real: Tensor, vq_indices: Optional[Tensor], beta_rate, beta_vq):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Stage-3 GAN training of DC-VIC on MI355X -- counterpart of the reference's scripts/train.py:16-27 +
+"""Stage-3 / 1-3 GAN training and stage 1-2 rate-distortion training of DC-VIC on MI355X -- counterpart of the reference's scripts/train.py:16-27 +
 src/trainer/base_trainer.py:130-152 (train_loop) for the `DualBetaCondGanDistortionVqCodeTrainer` of config/exp1_stage3.yaml.
 
     python scripts/train.py CONFIG [--model_path CKPT | --synthetic_weights] [--dataset_root DIR | --synthetic_data]
@@ -16,7 +16,7 @@ their stage-3 values (g_scheduler and d_scheduler milestones are read separately
 honoured or refused before any GPU work (dc_vic_amd/train/losses.py read_loss_section: CrossEntropyLoss / FocalCrossEntropyLoss,
 MSELoss normalize_img / mse_scale, VanillaMSELoss reduction, LPIPSLoss alex); rank 0 prints them as `[train] losses: ...`.
 Without `model.use_selected_beta_pairs` (config/exp1_stage1_3.yaml) beta_rate and beta_vq are drawn per sample from the
-(num_beta_levels + 1)-point grids; `trainer.beta_policy` / `trainer.beta_offset` are read by no GAN trainer of the reference and ignored.  LPIPS: pass --lpips_path (a torch.save'd state
+(num_beta_levels + 1)-point grids; `trainer.beta_policy` / `trainer.beta_offset` are read by no GAN trainer of the reference and ignored there.  LPIPS: pass --lpips_path (a torch.save'd state
 dict of lpips.LPIPS(net='alex'), loaded with weights_only=True); its weights cannot be fetched offline, so without it a positive
 perceptual weight is an ERROR unless --allow_synthetic_lpips opts into synthetic AlexNet weights (benchmarks / plumbing only).
 --save_step also writes training_state_iter*.pth.tar (Adam moments, step counts, scheduler epochs, beta-sampler RNG; the
@@ -28,6 +28,12 @@ Validation (base_trainer.py:130-192): every --eval_step iterations (YAML `eval_s
 GAN loss: `DualBetaCondGanDistortionVqCodeTrainer` (PatchGAN, VanillaGANLoss) or `DualBetaCondOasisGanDistortionVqFusionTrainer`
 (config/dc_vic_oasis.yaml: 257-way per-token discriminator, OasisGANLoss), chosen by --gan {vanilla,oasis}, else the YAML's
 `trainer.type`, else `loss.gan_loss.type`, else the discriminator's `out_nc` (1 -> vanilla, n_embed + 1 -> oasis); see choose_gan_trainer.
+Rate-distortion (config/exp1_stage1_2.yaml): `trainer.type: DualBetaCondRateDistortionVqCodeTrainer` builds dc_vic_amd/train/rd_trainer.py
+(choose_trainer, in front of choose_gan_trainer): the whole model but the VQGAN trains on rate + distortion + perceptual + code losses with
+per-sample weights exp(beta) or beta + offset (`trainer.beta_policy`, `beta_offset`, `sample_beta_batch`; `loss.rate_loss` and the
+`reduction: none` entries are read), `optim.aux_optimizer.lr` drives the entropy bottleneck's quantiles.  No discriminator is built and
+no discriminator_* file is written or read; --gan with such a config is an error, and so is the stage 1-1 `RateDistortionVqCodeTrainer`
+(an unconditioned model that is not built).  A stage 1-2 run starts from a dual-conditioned checkpoint (--model_path) or synthetic weights.
 """
 from __future__ import annotations
 
@@ -110,6 +116,55 @@ def choose_gan_trainer(opt, gan_flag=None):
     return kind, (OASIS_TRAINER if kind == "oasis" else VANILLA_TRAINER), reason
 
 
+RD_TRAINER, RD_STAGE_1_1 = "DualBetaCondRateDistortionVqCodeTrainer", "RateDistortionVqCodeTrainer"
+
+
+def choose_trainer(opt, gan_flag=None):
+    """(kind, trainer class name, reason) for a parsed config (pure: no GPU, no model): kind "rd" for the stage 1-2 rate-distortion
+    trainer (`trainer.type: DualBetaCondRateDistortionVqCodeTrainer`), else choose_gan_trainer's answer.  SystemExit for the stage 1-1
+    trainer (not built), for --gan together with a rate-distortion trainer type, and for what that trainer does not build."""
+    t_type = _get(opt, "trainer", "type")
+    if t_type == RD_STAGE_1_1:
+        raise SystemExit(f"trainer.type: {t_type} (stage 1-1, config/exp1_stage1_1.yaml) is not built: it trains the unconditioned model, which needs "
+                         "HyperpriorCharmVicModel, ElicVqCatScEncoder, ElicFeatFusionDecoder and LinearWarmupScheduler; the dual-conditioned "
+                         f"stage 1-2 trainer {RD_TRAINER} is")
+    if t_type != RD_TRAINER:
+        return choose_gan_trainer(opt, gan_flag)
+    if gan_flag is not None:
+        raise SystemExit(f"--gan {gan_flag} cannot go with trainer.type: {t_type}: the rate-distortion trainer has no discriminator and no GAN loss")
+    if _get(opt, "model", "gumbel_sampling", default=False):
+        raise SystemExit("model.gumbel_sampling: true is not built (the Gumbel-softmax sampling of the VQ indices in training mode): set it to false")
+    policy = _get(opt, "trainer", "beta_policy", default="linear")
+    if policy not in ("linear", "exp"):
+        raise SystemExit(f"trainer.beta_policy: {policy} is unknown, expected linear or exp")
+    if _get(opt, "loss", "gan_loss") is not None:
+        raise SystemExit(f"loss.gan_loss has no place under trainer.type: {t_type}: it trains no GAN loss")
+    return "rd", RD_TRAINER, f"trainer.type: {t_type}"
+
+
+def build_rd_trainer(opt, losses, model, dist, seed, lpips_state):
+    """The rate-distortion trainer from the YAML's `trainer`, `optim` and `loss` sections -> (trainer, the `[train]` log line)."""
+    from dc_vic_amd.train.rd_trainer import DEFAULT_RD_LOSS
+    lw = {k: v for k, v in losses["weights"].items() if k in DEFAULT_RD_LOSS}
+    rate = losses["rate"] or dict(loss_weight=None, reduction="mean")
+    if rate["loss_weight"] is not None:
+        lw["rate"] = rate["loss_weight"]
+    kw = dict(beta_policy=_get(opt, "trainer", "beta_policy", default="linear"), beta_offset=float(_get(opt, "trainer", "beta_offset", default=1.0)),
+              sample_beta_batch=bool(_get(opt, "trainer", "sample_beta_batch", default=False)), rate_reduction=rate["reduction"],
+              code_ce_gamma=losses["code_ce"]["gamma"], code_ce_reduction=losses["code_ce"]["reduction"],
+              code_distortion_reduction=losses["code_distortion_reduction"])
+    trainer = TRAINER_REGISTRY.get(RD_TRAINER)(
+        model, lr=float(_get(opt, "optim", "g_optimizer", "lr", default=1e-4)), aux_lr=float(_get(opt, "optim", "aux_optimizer", "lr", default=1e-3)),
+        milestones=list(_get(opt, "optim", "g_scheduler", "milestones", default=[300000])), gamma=float(_get(opt, "optim", "g_scheduler", "gamma", default=0.1)),
+        clip_max_norm=_get(opt, "optim", "clip_max_norm", default=1.0), loss_weights=lw, dist=dist, seed=seed, lpips_state=lpips_state,
+        distortion_factor=losses["distortion_factor"], gumbel_sampling=bool(_get(opt, "model", "gumbel_sampling", default=False)), **kw)
+    line = (f"rate-distortion trainer: {RD_TRAINER}; beta_policy {kw['beta_policy']}" + (f" (offset {kw['beta_offset']:g})" if kw["beta_policy"] == "linear" else "")
+            + f", sample_beta_batch {kw['sample_beta_batch']}; weights " + ", ".join(f"{k} {trainer.w[k]:g}" for k in DEFAULT_RD_LOSS)
+            + f"; reductions rate {kw['rate_reduction']}, code_distortion {kw['code_distortion_reduction']}, code_ce {kw['code_ce_reduction']}"
+            + f" (gamma {kw['code_ce_gamma']:g})")
+    return trainer, line
+
+
 class CropDataset:
     """OpenImages-style folder -> random 256 crops, flips, [-1, 1]; sharded by rank, reshuffled every epoch."""
 
@@ -169,7 +224,7 @@ def main():
     p.add_argument("--gan", choices=("vanilla", "oasis"), default=None, help="GAN loss / trainer (default: from the YAML, see choose_gan_trainer)")
     a = p.parse_args()
     opt0 = BaseConfig.fromfile(a.config_path, {"is_train": True})
-    gan_kind, trainer_name, gan_reason = choose_gan_trainer(opt0, a.gan)   # before any GPU work
+    gan_kind, trainer_name, gan_reason = choose_trainer(opt0, a.gan)       # before any GPU work
     losses = read_loss_section(opt0)                                       # likewise: every `loss` entry is honoured or refused
     if a.eval_dataset_root is not None:
         try:                                          # a folder named on the command line must hold PNGs: checked before any GPU work
@@ -208,12 +263,13 @@ def main():
         load_synth_weights(model, 1234)
     else:
         model.load_learned_weight(ckpt_path=a.model_path)
+    is_rd = gan_kind == "rd"                          # no discriminator, no discriminator_* file
     dopt = dict(_get(opt, "discriminator", default=None) or dict(type="DualBetaCondTamingNLayerDiscriminator", input_nc=11, n_layers=3, ndf=64,
                                                                   norm_type="none", max_beta_1=3.0, max_beta_2=3.5, L=10, cond_ch=8,
                                                                   use_pi=False, include_x=True))
     dopt.pop("type", None)
     torch.manual_seed(a.seed)                       # identical D initialisation on every rank
-    D = DualBetaCondTamingNLayerDiscriminator(**dopt).to(device)
+    D = None if is_rd else DualBetaCondTamingNLayerDiscriminator(**dopt).to(device)
     lw = dict(losses["weights"])
     from dc_vic_amd.train.trainer import DEFAULT_LOSS
     w_perc = lw.get("perceptual", DEFAULT_LOSS["perceptual"])
@@ -227,19 +283,25 @@ def main():
             raise SystemExit(msg + "  Pass --lpips_path STATE_DICT, set loss.perceptual_loss.loss_weight: 0, or opt in with --allow_synthetic_lpips.")
         if rank == 0:
             print("[train] WARNING: " + msg, file=sys.stderr, flush=True)
-    if rank == 0:
-        w_src = "loss.gan_loss.loss_weight" if "gan" in lw else "default, no reference YAML pins it" if gan_kind == "oasis" else "default"
-        print(f"[train] GAN trainer: {gan_kind} ({trainer_name}), chosen by {gan_reason}; generator-side gan weight "
-              f"{lw.get('gan', DEFAULT_LOSS['gan']):g} ({w_src})", flush=True)
-        print("[train] losses: " + losses["line"] + "; weights " + ", ".join(f"{k} {lw.get(k, v):g}" for k, v in DEFAULT_LOSS.items()), flush=True)
-    trainer = TRAINER_REGISTRY.get(trainer_name)(
-        model, D, lr_g=float(_get(opt, "optim", "g_optimizer", "lr", default=1e-4)), lr_d=float(_get(opt, "optim", "d_optimizer", "lr", default=1e-4)),
-        milestones=list(_get(opt, "optim", "g_scheduler", "milestones", default=[300000])), gamma=float(_get(opt, "optim", "g_scheduler", "gamma", default=0.1)),
-        clip_max_norm=_get(opt, "optim", "clip_max_norm", default=1.0), loss_weights=lw,
-        sample_beta_batch=bool(_get(opt, "trainer", "sample_beta_batch", default=True)), dist=dist, seed=a.seed * 100 + rank,
-        d_milestones=_get(opt, "optim", "d_scheduler", "milestones", default=None), d_gamma=_get(opt, "optim", "d_scheduler", "gamma", default=None),
-        lpips_state=lpips_state, code_ce_loss=build_code_ce_loss(losses["code_ce"], lw.get("code_ce", DEFAULT_LOSS["code_ce"])),
-        distortion_factor=losses["distortion_factor"], code_distortion_reduction=losses["code_distortion_reduction"])
+    if is_rd:
+        trainer, rd_line = build_rd_trainer(opt, losses, model, dist, a.seed * 100 + rank, lpips_state)
+        if rank == 0:
+            print("[train] " + rd_line, flush=True)
+            print("[train] losses: " + losses["line"], flush=True)
+    else:
+        if rank == 0:
+            w_src = "loss.gan_loss.loss_weight" if "gan" in lw else "default, no reference YAML pins it" if gan_kind == "oasis" else "default"
+            print(f"[train] GAN trainer: {gan_kind} ({trainer_name}), chosen by {gan_reason}; generator-side gan weight "
+                  f"{lw.get('gan', DEFAULT_LOSS['gan']):g} ({w_src})", flush=True)
+            print("[train] losses: " + losses["line"] + "; weights " + ", ".join(f"{k} {lw.get(k, v):g}" for k, v in DEFAULT_LOSS.items()), flush=True)
+        trainer = TRAINER_REGISTRY.get(trainer_name)(
+            model, D, lr_g=float(_get(opt, "optim", "g_optimizer", "lr", default=1e-4)), lr_d=float(_get(opt, "optim", "d_optimizer", "lr", default=1e-4)),
+            milestones=list(_get(opt, "optim", "g_scheduler", "milestones", default=[300000])), gamma=float(_get(opt, "optim", "g_scheduler", "gamma", default=0.1)),
+            clip_max_norm=_get(opt, "optim", "clip_max_norm", default=1.0), loss_weights=lw,
+            sample_beta_batch=bool(_get(opt, "trainer", "sample_beta_batch", default=True)), dist=dist, seed=a.seed * 100 + rank,
+            d_milestones=_get(opt, "optim", "d_scheduler", "milestones", default=None), d_gamma=_get(opt, "optim", "d_scheduler", "gamma", default=None),
+            lpips_state=lpips_state, code_ce_loss=build_code_ce_loss(losses["code_ce"], lw.get("code_ce", DEFAULT_LOSS["code_ce"])),
+            distortion_factor=losses["distortion_factor"], code_distortion_reduction=losses["code_distortion_reduction"])
     start_iter = 0
     if a.resume:
         # base_trainer.py:178-214: comp_model / discriminator / training_state files of one iteration
@@ -247,7 +309,8 @@ def main():
         d_ = os.path.dirname(a.resume)
         it_tag = os.path.basename(a.resume).replace("training_state_", "")
         model.load_state_dict(torch.load(os.path.join(d_, "comp_model_" + it_tag), map_location="cpu", weights_only=True)["comp_model"])
-        D.load_state_dict(torch.load(os.path.join(d_, "discriminator_" + it_tag), map_location="cpu", weights_only=True)["discriminator"])
+        if not is_rd:
+            D.load_state_dict(torch.load(os.path.join(d_, "discriminator_" + it_tag), map_location="cpu", weights_only=True)["discriminator"])
         trainer.resync_parameters()
         start_iter = trainer.load_training_state(st)
     total_iter = a.total_iter or int(_get(opt, "total_iter", default=500000))
@@ -302,8 +365,9 @@ def main():
         if a.save_dir and a.save_step and it % a.save_step == 0 and rank == 0:
             torch.save({"iter": it, "comp_model": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}},
                        os.path.join(a.save_dir, f"comp_model_iter{it:07d}.pth.tar"))
-            torch.save({"iter": it, "discriminator": {k: v.detach().cpu().clone() for k, v in D.state_dict().items()}},
-                       os.path.join(a.save_dir, f"discriminator_iter{it:07d}.pth.tar"))
+            if not is_rd:
+                torch.save({"iter": it, "discriminator": {k: v.detach().cpu().clone() for k, v in D.state_dict().items()}},
+                           os.path.join(a.save_dir, f"discriminator_iter{it:07d}.pth.tar"))
             torch.save(trainer.training_state(it), os.path.join(a.save_dir, f"training_state_iter{it:07d}.pth.tar"))
     if dist is not None:
         dist.barrier()

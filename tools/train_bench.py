@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """samples/s of the stage-3 training step (BASELINE config 5: 256x256 crops, batch 8 per GPU, G + D step) -- a SEPARATE metric,
-never mixed into bench.py's headline.  python tools/train_bench.py [--gan {vanilla,oasis}] [--batch 8] [--steps 5] [--warmup 2]
-(--gan oasis: the 257-class per-token discriminator of config/dc_vic_oasis.yaml and the OASIS cross-entropy loss); under
+never mixed into bench.py's headline.  python tools/train_bench.py [--gan {vanilla,oasis} | --stage 1_2] [--batch 8] [--steps 5] [--warmup 2]
+(--gan oasis: the 257-class per-token discriminator of config/dc_vic_oasis.yaml and the OASIS cross-entropy loss; --stage 1_2: the
+rate-distortion step of train/rd_trainer.py with config/exp1_stage1_2.yaml's trainer and loss sections, no discriminator); under
 torch.distributed.run it is data-parallel (weak scaling) and reports the aggregate."""
 import argparse
 import json
@@ -21,6 +22,7 @@ def main():
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--gan", choices=("vanilla", "oasis"), default="vanilla")
+    p.add_argument("--stage", choices=("3", "1_2"), default="3", help="3: the G + D step (default); 1_2: the rate-distortion step")
     a = p.parse_args()
     rank, world, lr_ = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(lr_)
@@ -33,15 +35,12 @@ def main():
         dist = dist_
     from dc_vic_amd import BaseConfig, build_comp_model
     from dc_vic_amd.synth import load_synth_weights
-    from dc_vic_amd.train import (DualBetaCondGanDistortionVqCodeTrainer, DualBetaCondOasisGanDistortionVqFusionTrainer,
-                                  DualBetaCondTamingNLayerDiscriminator)
     m = build_comp_model(BaseConfig.fromfile(os.path.join(ROOT, "config", "dc_vic_synthetic.yaml"), {"device": dev}))
     load_synth_weights(m, 1234)
-    torch.manual_seed(0)
-    dkw = dict(out_nc=m.vq_model.quantize.embedding.weight.shape[0] + 1, keep_shape=True) if a.gan == "oasis" else {}
-    D = DualBetaCondTamingNLayerDiscriminator(input_nc=11, n_layers=3, ndf=64, norm_type="none", max_beta_1=3.0, max_beta_2=3.5, **dkw).to(dev)
-    cls = DualBetaCondOasisGanDistortionVqFusionTrainer if a.gan == "oasis" else DualBetaCondGanDistortionVqCodeTrainer
-    tr = cls(m, D, dist=dist, seed=rank)
+    if a.stage == "1_2":
+        tr, what = rd_trainer(m, dist, rank), "stage 1-2 rate-distortion step"
+    else:
+        tr, what = gan_trainer(a, m, dev, dist, rank), "stage-3 G+D step"
     g = torch.Generator().manual_seed(100 + rank)
     x = torch.rand((a.batch, 3, 256, 256), generator=g) * 2 - 1
     for _ in range(a.warmup):
@@ -57,12 +56,36 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     if rank == 0:
-        print(json.dumps({"metric": "training samples/sec, stage-3 G+D step @256x256", "value": world * a.batch * a.steps / dt, "unit": "samples/s",
-                          "gan": a.gan, "n_gpus": world, "steps": a.steps, "ms_per_step": 1e3 * dt / a.steps, "batch_per_gpu": a.batch, "dtype": "f32",
+        print(json.dumps({"metric": f"training samples/sec, {what} @256x256", "value": world * a.batch * a.steps / dt, "unit": "samples/s",
+                          "gan": a.gan if a.stage == "3" else None, "stage": a.stage, "n_gpus": world, "steps": a.steps, "ms_per_step": 1e3 * dt / a.steps,
+                          "batch_per_gpu": a.batch, "dtype": "f32",
                           "data": "synthetic", "lpips": "included, synthetic weights (parity unpinned)", "last_log": log}), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 
+
+def rd_trainer(m, dist, rank):
+    from dc_vic_amd.train import DualBetaCondRateDistortionVqCodeTrainer
+    from dc_vic_amd.train.losses import read_loss_section
+    with open(os.path.join(ROOT, "tests", "golden", "reference_loss_sections.json")) as f:
+        opt = json.load(f)["exp1_stage1_2.yaml"]
+    r = read_loss_section(opt)
+    lw = {k: v for k, v in r["weights"].items() if k != "gan"}
+    lw["rate"] = r["rate"]["loss_weight"]
+    return DualBetaCondRateDistortionVqCodeTrainer(
+        m, loss_weights=lw, beta_policy=opt["trainer"]["beta_policy"], sample_beta_batch=opt["trainer"]["sample_beta_batch"], dist=dist, seed=rank,
+        rate_reduction=r["rate"]["reduction"], code_ce_gamma=r["code_ce"]["gamma"], code_ce_reduction=r["code_ce"]["reduction"],
+        code_distortion_reduction=r["code_distortion_reduction"], distortion_factor=r["distortion_factor"])
+
+
+def gan_trainer(a, m, dev, dist, rank):
+    from dc_vic_amd.train import (DualBetaCondGanDistortionVqCodeTrainer, DualBetaCondOasisGanDistortionVqFusionTrainer,
+                                  DualBetaCondTamingNLayerDiscriminator)
+    torch.manual_seed(0)
+    dkw = dict(out_nc=m.vq_model.quantize.embedding.weight.shape[0] + 1, keep_shape=True) if a.gan == "oasis" else {}
+    D = DualBetaCondTamingNLayerDiscriminator(input_nc=11, n_layers=3, ndf=64, norm_type="none", max_beta_1=3.0, max_beta_2=3.5, **dkw).to(dev)
+    cls = DualBetaCondOasisGanDistortionVqFusionTrainer if a.gan == "oasis" else DualBetaCondGanDistortionVqCodeTrainer
+    return cls(m, D, dist=dist, seed=rank)
 
 if __name__ == "__main__":
     main()

@@ -1,5 +1,5 @@
 """ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h, include/dcvic_rate.h, include/dcvic_train.h, include/dcvic_vq.h,
-include/dcvic_sample_loss.h).  The library is REQUIRED: there is no
+include/dcvic_sample_loss.h, include/dcvic_gumbel.h).  The library is REQUIRED: there is no
 fallback path -- if it is missing or an entry point fails, the caller gets an exception."""
 from __future__ import annotations
 
@@ -123,6 +123,10 @@ SAMPLE_LOSS_SIGNATURES = {
     "dcvic_focal_ce_sample_workspace_doubles": "q:ii", "dcvic_focal_ce_sample_f32": "i:pppdppppiiip",
     "dcvic_sq_err_sample_workspace_doubles": "q:iq", "dcvic_sq_err_sample_f32": "i:pqppppppiqp",
 }
+# include/dcvic_gumbel.h: the hard Gumbel-softmax VQ sample of training mode and its straight-through gradient (csrc/gumbel.hip)
+GUMBEL_SIGNATURES = {
+    "dcvic_gumbel_lut_f32": "i:pppppppdiiiip", "dcvic_gumbel_lut_bwd_f32": "i:pppppdpiiiip",
+}
 VQ_NONE, VQ_SHARD, VQ_PACKED2, VQ_PACKED1, VQ_LDS4, VQ_LDS8 = range(6)
 
 _lib = None
@@ -143,7 +147,7 @@ def lib() -> C.CDLL:
             "(or __graft_entry__.build()). dc_vic_amd has no fallback path.")
     L = C.CDLL(LIB_PATH)
     for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items(), *RATE_SIGNATURES.items(), *TRAIN_SIGNATURES.items(), *VQ_SIGNATURES.items(),
-                      *SAMPLE_LOSS_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
+                      *SAMPLE_LOSS_SIGNATURES.items(), *GUMBEL_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
         fn = getattr(L, name)                # AttributeError names a symbol the library lacks
         ret, params = sig.split(":")
         fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[c] for c in params]

@@ -331,6 +331,8 @@ class HyperpriorVicModel(BaseModel):
         if enc_vq_input != "onehot_indices" or enc_input_vq_recon:
             raise NotImplementedError("only enc_vq_input='onehot_indices' (the shipped configs) is built")
         self.enc_vq_input = enc_vq_input
+        # training mode only (hyperprior_vic_model.py:393-406): read by the GAN-stage trainers, never by an inference path
+        self.gumbel_sampling, self.gumbel_kwargs = bool(gumbel_sampling), dict(gumbel_kwargs or {})
         self.n_embed = self.vq_model.n_embed
         self.model_stride, self.y_stride = 64, 16
         self._decoder_precision = "fp32"

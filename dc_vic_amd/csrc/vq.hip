@@ -13,6 +13,7 @@
 // Roofline: 16 B read + 8 B index (+16 B z_q, + (D+n_e)*4 B one-hot feature when requested) per vector.
 #include "common.h"
 #include "dcvic_vq.h"
+#include "vq_lut.h"
 
 #define VQ_MAXD 8
 
@@ -355,12 +356,7 @@ __global__ __launch_bounds__(256) void argmax_lut_kernel(const float* __restrict
     }
     if (idx) idx[(long long)n * HW + p] = (int64_t)bi;
     if (latent) {
-        for (int c = 0; c < D; ++c) {
-            float a = 0.f;
-            for (int d = 0; d < D; ++d) a = fmaf(pq_w[c * D + d], cb[bi * D + d], a);
-            if (pq_b) a += pq_b[c];
-            latent[(long long)n * D * HW + (long long)c * HW + p] = a;
-        }
+        for (int c = 0; c < D; ++c) latent[(long long)n * D * HW + (long long)c * HW + p] = dcvic_lut_latent(cb, pq_w, pq_b, bi, c, D);
     }
 }
 

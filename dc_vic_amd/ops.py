@@ -683,6 +683,22 @@ def argmax_lut(logits: Tensor, codebook: Tensor, pq_w: Tensor, pq_b: Optional[Te
     return idx, lat
 
 
+def gumbel_lut(logits: Tensor, noise: Tensor, codebook: Tensor, pq_w: Tensor, pq_b: Optional[Tensor], tau: float = 1.0):
+    """The hard Gumbel-softmax sample of training mode (F.gumbel_softmax(logits, tau, hard=True, dim=1) for the draw `noise` ~ Exp(1),
+    times the codebook, through post_quant_conv): idx = first argmax of logits - log(noise), lat as argmax_lut forms it."""
+    N, n_e, H, W = _chk4(logits, "gumbel logits")
+    if not logits.is_contiguous() or not noise.is_contiguous() or tuple(noise.shape) != tuple(logits.shape) or noise.dtype != torch.float32:
+        raise ValueError(f"gumbel_lut needs contiguous fp32 logits and noise of one shape, got {tuple(logits.shape)} and {tuple(noise.shape)}")
+    if tuple(codebook.shape[:1]) != (n_e,) or not codebook.is_contiguous() or not pq_w.is_contiguous():
+        raise ValueError(f"gumbel_lut: codebook {tuple(codebook.shape)} for {n_e} classes")
+    D = codebook.shape[1]
+    idx = torch.empty((N, H, W), dtype=torch.int64, device=logits.device)
+    lat = new(N, D, H, W, logits)
+    check(lib().dcvic_gumbel_lut_f32(_p(logits), _p(noise), _p(idx), _p(lat), _p(codebook), _p(pq_w), _p(pq_b), float(tau), N, n_e, D, H * W,
+                                     _stream()), "gumbel_lut")
+    return idx, lat
+
+
 # ------------------------------------------------------------------------------------------- rate
 def gaussian_rate(y: Optional[Tensor], sym_in: Optional[Tensor], mu: Tensor, sigma: Tensor, scale_table: Tensor,
                   y_hat: Optional[Tensor], sym_out: Optional[Tensor], index_out: Optional[Tensor], lik_out: Optional[Tensor],

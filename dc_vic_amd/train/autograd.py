@@ -550,6 +550,17 @@ def oasis_gan_loss(ctx: Ctx, logits: Var, target: Tensor, is_real: bool, weight:
     return (val, score) if want_score else val
 
 
+# ------------------------------------------------------------------------------------------- Gumbel-softmax VQ sample (csrc/gumbel.hip)
+def gumbel_vq_latent(ctx: Ctx, logits: Var, noise: Tensor, codebook: Tensor, pq_w: Tensor, pq_b: Optional[Tensor], tau: float = 1.0):
+    """hyperprior_dc_vic_model.py:254-260 with model.gumbel_sampling: the hard Gumbel-softmax sample of the code logits for the draw
+    `noise` ~ Exp(1) (F.gumbel_softmax(logits, tau, hard=True, dim=1)), times the detached codebook, through the frozen post_quant_conv.
+    -> (idx, latent Var).  A gradient arriving on the latent reaches `logits` through the straight-through softmax (the codebook and
+    post_quant_conv take none); the softmax is recomputed from `logits` and `noise` in the backward kernel."""
+    ld = _dense(logits.data)
+    idx, lat = ops.gumbel_lut(ld, noise, codebook, pq_w, pq_b, tau)
+    return idx, ctx.op(lat, lambda g: acc(logits, K.gumbel_lut_bwd(ld, noise, _dense(g), codebook, pq_w, tau)), needs_grad=logits.needs_grad)
+
+
 # ------------------------------------------------------------------------------------------- the rate term (csrc/rate_train.hip)
 def gaussian_rate(ctx: Ctx, y: Var, mu: Var, sigma: Var, noise: Tensor, weights: Optional[Tensor], scale: float, bits: Optional[Tensor],
                   loss: Optional[Tensor], dy_out: Optional[Tensor] = None, lik_out: Optional[Tensor] = None) -> Var:

@@ -1,5 +1,5 @@
 """ctypes wrappers of the training-step kernels (csrc/train.hip, include/dcvic.h "Training step"; csrc/chan_ce.hip; csrc/sample_loss.hip,
-include/dcvic_sample_loss.h; csrc/rate_train.hip, include/dcvic_rate.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
+include/dcvic_sample_loss.h; csrc/rate_train.hip, include/dcvic_rate.h; csrc/gumbel.hip, include/dcvic_gumbel.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
 from __future__ import annotations
 
 import ctypes
@@ -227,6 +227,20 @@ def sq_err_sample(a: Tensor, b: Tensor, w: Tensor, want_grad: bool = True, want_
 
 
 # ------------------------------------------------------------------------------------------- the rate term (csrc/rate_train.hip)
+def gumbel_lut_bwd(logits: Tensor, noise: Tensor, glatent: Tensor, codebook: Tensor, pq_w: Tensor, tau: float) -> Tensor:
+    """dlogits of ops.gumbel_lut's latent for a gradient `glatent` [N, D, H, W] on it: s_j * (v_j - sum_k s_k v_k) / tau with
+    s = softmax((logits - log(noise)) / tau) recomputed and v_j = codebook[j] . (pq_w^T glatent)  (dcvic_gumbel_lut_bwd_f32)."""
+    N, n_e, H, W = _chk4(logits, "gumbel_bwd logits")
+    D = int(codebook.shape[1])
+    if not (logits.is_contiguous() and noise.is_contiguous() and glatent.is_contiguous() and codebook.is_contiguous() and pq_w.is_contiguous()) \
+            or tuple(noise.shape) != tuple(logits.shape) or tuple(glatent.shape) != (N, D, H, W) or int(codebook.shape[0]) != n_e:
+        raise ValueError(f"gumbel_lut_bwd: logits {tuple(logits.shape)} noise {tuple(noise.shape)} glatent {tuple(glatent.shape)} codebook {tuple(codebook.shape)}")
+    dl = torch.empty_like(logits)
+    check(lib().dcvic_gumbel_lut_bwd_f32(_p(logits), _p(noise), _p(glatent), _p(codebook), _p(pq_w), float(tau), _p(dl), N, n_e, D, H * W, _stream()),
+          "gumbel_lut_bwd")
+    return dl
+
+
 EB_PARAM_NAMES = tuple(f"_matrix{i}" for i in range(5)) + tuple(f"_bias{i}" for i in range(5)) + tuple(f"_factor{i}" for i in range(4))
 _EB_WIDTH = (3, 9, 9, 9, 3, 3, 3, 3, 3, 1, 3, 3, 3, 3)
 

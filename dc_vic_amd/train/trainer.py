@@ -82,6 +82,19 @@ def loss_anomaly(total: float, dist, device=None) -> bool:
     return bool(flag.item() > 0)
 
 
+def gumbel_tau(gumbel_kwargs: Optional[Dict]) -> float:
+    """`tau` of model.gumbel_kwargs (default 1).  The trainer's sample is F.gumbel_softmax(logits, dim=1, hard=True, tau=tau): `tau` is the
+    only keyword it can honour (`hard` and `dim` would collide with the reference's own arguments, `eps` is deprecated and unused)."""
+    kw = dict(gumbel_kwargs or {})
+    tau = kw.pop("tau", 1.0)
+    if kw:
+        k = sorted(kw)[0]
+        raise ValueError(f"model.gumbel_kwargs.{k}: {kw[k]!r} is not built: tau is the only keyword of the Gumbel-softmax sample")
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not math.isfinite(tau) or tau <= 0:
+        raise ValueError(f"model.gumbel_kwargs.tau: {tau!r} is not a finite number > 0")
+    return float(tau)
+
+
 class MultiStepLR:
     def __init__(self, base_lr: float, milestones: List[int], gamma: float):
         self.base_lr, self.milestones, self.gamma, self.last_epoch = base_lr, sorted(milestones), gamma, 0
@@ -182,10 +195,14 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
     def __init__(self, model, discriminator, lr_g: float = 1e-4, lr_d: float = 1e-4, milestones=(300000,), gamma: float = 0.1,
                  clip_max_norm: Optional[float] = 1.0, loss_weights: Optional[Dict[str, float]] = None, sample_beta_batch: bool = True,
                  dist=None, seed: int = 0, d_milestones=None, d_gamma: Optional[float] = None, lpips_state: Optional[Dict[str, Tensor]] = None,
-                 code_ce_loss=None, distortion_factor: float = 0.25, code_distortion_reduction: str = "mean"):
+                 code_ce_loss=None, distortion_factor: float = 0.25, code_distortion_reduction: str = "mean",
+                 gumbel_sampling: Optional[bool] = None, gumbel_kwargs: Optional[Dict] = None):
         """`code_ce_loss`: a loss object of train/losses.py (CrossEntropyLoss / FocalCrossEntropyLoss, carrying its own weight) or None
         for CrossEntropyLoss x loss_weights['code_ce']; `distortion_factor`: MSELoss's factor on mean((a - b)^2) of the [-1, 1] images
-        (0.25 = the [0, 1] scale of the shipped configs); `code_distortion_reduction`: VanillaMSELoss's mean or sum."""
+        (0.25 = the [0, 1] scale of the shipped configs); `code_distortion_reduction`: VanillaMSELoss's mean or sum;
+        `gumbel_sampling` / `gumbel_kwargs` (None: the model's attributes of those names): decode a hard Gumbel-softmax sample of the
+        code logits instead of their argmax (hyperprior_dc_vic_model.py:254-260), which lets the image losses reach the estimator; the
+        only keyword is `tau` (> 0, default 1).  The draws come from `self.gumbel_gen`, a device generator seeded like the beta sampler."""
         self.model, self.D = model, discriminator
         dev = next(model.decoder.parameters()).device
         self.device = dev
@@ -210,6 +227,12 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
         self.rng = np.random.RandomState(seed)
         self.last_fake: Optional[Tensor] = None
         self._build_lpips(self.w["perceptual"], lpips_state, dev)
+        self.gumbel_sampling = bool(getattr(model, "gumbel_sampling", False) if gumbel_sampling is None else gumbel_sampling)
+        self.gumbel_tau = 1.0
+        self.gumbel_gen: Optional[torch.Generator] = None         # exists only with the option on: no draw, no state without it
+        if self.gumbel_sampling:
+            self.gumbel_tau = gumbel_tau(getattr(model, "gumbel_kwargs", None) if gumbel_kwargs is None else gumbel_kwargs)
+            self.gumbel_gen = torch.Generator(device=dev).manual_seed(int(seed))
 
     # ---------------------------------------------------------------- training state (base_trainer.py:178-214 saves optimizer + scheduler state)
     def training_state(self, current_iter: int) -> Dict:
@@ -217,6 +240,8 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
         for tag, grp, opt_, sch in (("g", self.g_group, self.g_opt, self.g_sched), ("d", self.d_group, self.d_opt, self.d_sched)):
             st[tag] = {"m": grp.m.detach().cpu().clone(), "v": grp.v.detach().cpu().clone(), "t": int(opt_.t), "last_epoch": int(sch.last_epoch),
                        "numel": int(grp.numel())}
+        if self.gumbel_gen is not None:
+            st["gumbel_gen"] = self.gumbel_gen.get_state().clone()
         return st
 
     def load_training_state(self, st: Dict) -> int:
@@ -228,6 +253,10 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
             opt_.t, sch.last_epoch = int(s_["t"]), int(s_["last_epoch"])
         if "rng" in st:
             self.rng.set_state(st["rng"])
+        if self.gumbel_gen is not None:
+            if "gumbel_gen" not in st:
+                raise ValueError("training state: no gumbel_gen entry, it was saved by a run without model.gumbel_sampling")
+            self.gumbel_gen.set_state(st["gumbel_gen"].cpu())
         return int(st["iter"])
 
     def resync_parameters(self) -> None:
@@ -249,11 +278,21 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
         pred_embed, logits = nets.estimator_forward(ctx, m.vq_estimator, feat_1)
         pq = m.vq_model.post_quant_conv
         out_idx, lat = ops.argmax_lut(logits.data, m.vq_model.quantize.embedding.weight, pq.weight.reshape(pq.out_channels, -1).contiguous(), pq.bias)
-        fake = nets.fusion_decode(ctx, m.fusion_module, m.vq_model.decoder, A.const(lat), feats, w=1.0)
+        z = A.const(lat)
+        if self.gumbel_sampling:
+            # :254-260: the decoder reads the sample; out_vq_indices stays the argmax (vq_acc)
+            noise = self.draw_gumbel_noise(logits.data)
+            _, z = A.gumbel_vq_latent(ctx, logits, noise, m.vq_model.quantize.embedding.weight, pq.weight.reshape(pq.out_channels, -1).contiguous(),
+                                      pq.bias, self.gumbel_tau)
+        fake = nets.fusion_decode(ctx, m.fusion_module, m.vq_model.decoder, z, feats, w=1.0)
         N, _, H, W = x.shape
         qbpp = float((e["bits_y"].double().sum() + e["bits_z"].double().sum()).item()) / (N * H * W)
         return dict(real=x, fake=fake, pred_embed=pred_embed, logits=logits, gt_vq_latent=gt_lat, gt_vq_indices=gt_idx, out_vq_indices=out_idx,
                     y_hat=y_hat, qbpp=qbpp)
+
+    def draw_gumbel_noise(self, logits: Tensor) -> Tensor:
+        """e ~ Exp(1) of the logits' shape from the trainer's generator: -log(e) is the Gumbel noise F.gumbel_softmax draws."""
+        return torch.empty_like(logits).exponential_(generator=self.gumbel_gen)
 
     def calc_g_loss(self, ctx: Ctx, o: Dict, beta_rate, beta_vq) -> Dict[str, Tensor]:
         """:192-234; each term seeds its gradient on the tape."""

@@ -19,6 +19,10 @@ Without `model.use_selected_beta_pairs` (config/exp1_stage1_3.yaml) beta_rate an
 (num_beta_levels + 1)-point grids; `trainer.beta_policy` / `trainer.beta_offset` are read by no GAN trainer of the reference and ignored there.  LPIPS: pass --lpips_path (a torch.save'd state
 dict of lpips.LPIPS(net='alex'), loaded with weights_only=True); its weights cannot be fetched offline, so without it a positive
 perceptual weight is an ERROR unless --allow_synthetic_lpips opts into synthetic AlexNet weights (benchmarks / plumbing only).
+`model.gumbel_sampling: true` (GAN trainers only; the rate-distortion trainer refuses it): the decoder reads a hard Gumbel-softmax
+sample of the code logits instead of their argmax (csrc/gumbel.hip), so the distortion, perceptual and adversarial losses reach the VQ
+estimator; `model.gumbel_kwargs` may set `tau` (> 0, default 1) and nothing else (read_gumbel_options); the noise comes from a device
+generator the trainer owns, saved in and restored from the training state (rank 0's); rank 0 prints `[train] VQ sampling: ...`.
 --save_step also writes training_state_iter*.pth.tar (Adam moments, step counts, scheduler epochs, beta-sampler RNG; the
 reference saves optimizer + scheduler state too, base_trainer.py:178-214) and --resume continues from it.
 Validation (base_trainer.py:130-192): every --eval_step iterations (YAML `eval_step`, 0 = off) rank 0 runs the sorted *.png of
@@ -114,6 +118,20 @@ def choose_gan_trainer(opt, gan_flag=None):
         raise SystemExit(f"vanilla GAN loss ({reason}) cannot train a discriminator with out_nc: {out_nc} (n_embed + 1 classes: an OASIS "
                          "discriminator); use --gan oasis or out_nc: 1")
     return kind, (OASIS_TRAINER if kind == "oasis" else VANILLA_TRAINER), reason
+
+
+def read_gumbel_options(opt):
+    """(gumbel_sampling, tau) of a parsed config's `model` section for the GAN-stage trainers (pure: no GPU, no model), called after
+    choose_gan_trainer.  `model.gumbel_kwargs` may hold `tau` (a number > 0, default 1) and nothing else: the sample is the reference's
+    F.gumbel_softmax(logits, dim=1, hard=True, **gumbel_kwargs), so `hard` and `dim` would raise there and `eps` does nothing.
+    SystemExit names the key and its value.  The keywords are checked with the option off too, as the model's constructor takes them."""
+    from dc_vic_amd.train.trainer import gumbel_tau
+    kw = _get(opt, "model", "gumbel_kwargs", default=None)
+    try:
+        tau = gumbel_tau(dict(kw) if kw else None)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    return bool(_get(opt, "model", "gumbel_sampling", default=False)), tau
 
 
 RD_TRAINER, RD_STAGE_1_1 = "DualBetaCondRateDistortionVqCodeTrainer", "RateDistortionVqCodeTrainer"
@@ -226,6 +244,7 @@ def main():
     opt0 = BaseConfig.fromfile(a.config_path, {"is_train": True})
     gan_kind, trainer_name, gan_reason = choose_trainer(opt0, a.gan)       # before any GPU work
     losses = read_loss_section(opt0)                                       # likewise: every `loss` entry is honoured or refused
+    gumbel_on, gumbel_tau_ = read_gumbel_options(opt0) if gan_kind != "rd" else (False, 1.0)    # likewise
     if a.eval_dataset_root is not None:
         try:                                          # a folder named on the command line must hold PNGs: checked before any GPU work
             eval_image_paths(a.eval_dataset_root)
@@ -294,6 +313,7 @@ def main():
             print(f"[train] GAN trainer: {gan_kind} ({trainer_name}), chosen by {gan_reason}; generator-side gan weight "
                   f"{lw.get('gan', DEFAULT_LOSS['gan']):g} ({w_src})", flush=True)
             print("[train] losses: " + losses["line"] + "; weights " + ", ".join(f"{k} {lw.get(k, v):g}" for k, v in DEFAULT_LOSS.items()), flush=True)
+            print("[train] VQ sampling: " + (f"gumbel-softmax (tau {gumbel_tau_:g})" if gumbel_on else "argmax"), flush=True)
         trainer = TRAINER_REGISTRY.get(trainer_name)(
             model, D, lr_g=float(_get(opt, "optim", "g_optimizer", "lr", default=1e-4)), lr_d=float(_get(opt, "optim", "d_optimizer", "lr", default=1e-4)),
             milestones=list(_get(opt, "optim", "g_scheduler", "milestones", default=[300000])), gamma=float(_get(opt, "optim", "g_scheduler", "gamma", default=0.1)),
@@ -301,7 +321,8 @@ def main():
             sample_beta_batch=bool(_get(opt, "trainer", "sample_beta_batch", default=True)), dist=dist, seed=a.seed * 100 + rank,
             d_milestones=_get(opt, "optim", "d_scheduler", "milestones", default=None), d_gamma=_get(opt, "optim", "d_scheduler", "gamma", default=None),
             lpips_state=lpips_state, code_ce_loss=build_code_ce_loss(losses["code_ce"], lw.get("code_ce", DEFAULT_LOSS["code_ce"])),
-            distortion_factor=losses["distortion_factor"], code_distortion_reduction=losses["code_distortion_reduction"])
+            distortion_factor=losses["distortion_factor"], code_distortion_reduction=losses["code_distortion_reduction"],
+            gumbel_sampling=gumbel_on, gumbel_kwargs=dict(tau=gumbel_tau_))
     start_iter = 0
     if a.resume:
         # base_trainer.py:178-214: comp_model / discriminator / training_state files of one iteration

@@ -1,5 +1,5 @@
 """ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h, include/dcvic_rate.h, include/dcvic_train.h, include/dcvic_vq.h,
-include/dcvic_sample_loss.h, include/dcvic_gumbel.h).  The library is REQUIRED: there is no
+include/dcvic_sample_loss.h, include/dcvic_gumbel.h, include/dcvic_msssim_loss.h).  The library is REQUIRED: there is no
 fallback path -- if it is missing or an entry point fails, the caller gets an exception."""
 from __future__ import annotations
 
@@ -127,6 +127,11 @@ SAMPLE_LOSS_SIGNATURES = {
 GUMBEL_SIGNATURES = {
     "dcvic_gumbel_lut_f32": "i:pppppppdiiiip", "dcvic_gumbel_lut_bwd_f32": "i:pppppdpiiiip",
 }
+# include/dcvic_msssim_loss.h: the image distortions MSSSIMLoss and L1Loss of the rate-distortion trainer (csrc/msssim_loss.hip)
+MSSSIM_LOSS_SIGNATURES = {
+    "dcvic_msssim_loss_workspace_bytes": "q:iiii", "dcvic_msssim_loss_f32": "i:ppiiiidppppqp",
+    "dcvic_abs_err_workspace_bytes": "q:iq", "dcvic_abs_err_f32": "i:ppqidpppqp",
+}
 VQ_NONE, VQ_SHARD, VQ_PACKED2, VQ_PACKED1, VQ_LDS4, VQ_LDS8 = range(6)
 
 _lib = None
@@ -147,7 +152,7 @@ def lib() -> C.CDLL:
             "(or __graft_entry__.build()). dc_vic_amd has no fallback path.")
     L = C.CDLL(LIB_PATH)
     for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items(), *RATE_SIGNATURES.items(), *TRAIN_SIGNATURES.items(), *VQ_SIGNATURES.items(),
-                      *SAMPLE_LOSS_SIGNATURES.items(), *GUMBEL_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
+                      *SAMPLE_LOSS_SIGNATURES.items(), *GUMBEL_SIGNATURES.items(), *MSSSIM_LOSS_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
         fn = getattr(L, name)                # AttributeError names a symbol the library lacks
         ret, params = sig.split(":")
         fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[c] for c in params]

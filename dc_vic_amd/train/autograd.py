@@ -486,6 +486,35 @@ def mse_loss(ctx: Ctx, a: Var, target: Tensor, weight: float) -> Tensor:
     return val
 
 
+def l1_loss(ctx: Ctx, a: Var, target: Tensor, weight: float) -> Tensor:
+    """weight * mean|a - target| (distortion_loss.py `L1Loss`): value (fp64, 1 element) and gradient weight * sign(a - target) / numel,
+    sign(0) = 0, from one pass of csrc/msssim_loss.hip; the gradient is seeded into `a`."""
+    ad, td = _dense(a.data), _dense(target)
+    val, da = K.abs_err(ad, td, weight / ad.numel(), want_grad=a.needs_grad)
+    if da is not None:
+        acc(a, da)
+    return val
+
+
+MS_SSIM_MIN_SIDE = 160              # pytorch-msssim asserts min(H, W) > (11 - 1) * 2^4
+
+
+def ms_ssim_loss(ctx: Ctx, fake: Var, real: Tensor, weight: float) -> Tensor:
+    """weight * (1 - MS_SSIM(data_range=1, size_average=True, channel=3)(real, fake)) on the images as they are (distortion_loss.py
+    `MSSSIMLoss`, applied to the trainer's [-1, 1] images with `fake` unclamped): value (fp64, 1 element) and the gradient with respect
+    to `fake` from csrc/msssim_loss.hip, seeded into `fake`; `real` is a constant.  RGB only, min(H, W) > 160."""
+    fd, rd = _dense(fake.data), _dense(real)
+    if fd.dim() != 4 or fd.shape[1] != 3:
+        raise ValueError(f"ms_ssim_loss: RGB images [N, 3, H, W], got {tuple(fd.shape)}")
+    N, Cc, H, W = fd.shape
+    if min(H, W) <= MS_SSIM_MIN_SIDE:
+        raise ValueError(f"ms_ssim_loss: images of {H} x {W}, MS-SSIM over five scales needs min(H, W) > {MS_SSIM_MIN_SIDE}")
+    val, df, _ = K.ms_ssim_loss(rd, fd, weight / (N * Cc), want_grad=fake.needs_grad)
+    if df is not None:
+        acc(fake, df)
+    return val
+
+
 def bce_logits_loss(ctx: Ctx, x: Var, is_real: bool, weight: float) -> Tensor:
     """weight * BCEWithLogits(x, 1 or 0), mean reduction (src/losses/gan_loss.py:10-32)."""
     xd = _dense(x.data)

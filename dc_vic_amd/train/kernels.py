@@ -1,5 +1,5 @@
 """ctypes wrappers of the training-step kernels (csrc/train.hip, include/dcvic.h "Training step"; csrc/chan_ce.hip; csrc/sample_loss.hip,
-include/dcvic_sample_loss.h; csrc/rate_train.hip, include/dcvic_rate.h; csrc/gumbel.hip, include/dcvic_gumbel.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
+include/dcvic_sample_loss.h; csrc/rate_train.hip, include/dcvic_rate.h; csrc/gumbel.hip, include/dcvic_gumbel.h; csrc/msssim_loss.hip, include/dcvic_msssim_loss.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
 from __future__ import annotations
 
 import ctypes
@@ -224,6 +224,43 @@ def sq_err_sample(a: Tensor, b: Tensor, w: Tensor, want_grad: bool = True, want_
     check(lib().dcvic_sq_err_sample_f32(_p(a), a.stride(0) if N > 1 else M, _p(b), _p(_flat_f32(w, N, "sq_err_sample: sample weights")), _p(loss),
                                         _p(da), _p(per), _p(ws), N, M, _stream()), "sq_err_sample")
     return loss, da, per
+
+
+# ------------------------------------------------------------------------------------------- image distortions (csrc/msssim_loss.hip)
+def _image_pair(name: str, a: Tensor, b: Tensor) -> None:
+    for t, what in ((a, "first"), (b, "second")):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{name}: the {what} operand must be a contiguous fp32 device tensor, got {t.dtype} {tuple(t.shape)} {t.device}")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"{name}: operands of {tuple(a.shape)} and {tuple(b.shape)}")
+
+
+def ms_ssim_loss(real: Tensor, fake: Tensor, scale: float, want_grad: bool = True, want_per_plane: bool = False):
+    """scale * sum over the N*C planes of (1 - MS-SSIM(real, fake)) with data_range = 1 on the planes as they are (dcvic_msssim_loss_f32):
+    (loss: fp64 [1], dfake or None, per_plane: fp64 [N, C] MS-SSIM values or None); `real` is a constant.  [N, C, H, W], min(H, W) > 160."""
+    _image_pair("ms_ssim_loss", real, fake)
+    N, Cc, H, W = _chk4(fake, "ms_ssim_loss fake")
+    need = int(lib().dcvic_msssim_loss_workspace_bytes(N, Cc, H, W))
+    ws = _workspace((need + 7) // 8, fake.device, "msssim_loss", torch.float64)
+    loss = torch.empty(1, dtype=torch.float64, device=fake.device)
+    df = torch.empty_like(fake) if want_grad else None
+    per = torch.empty((N, Cc), dtype=torch.float64, device=fake.device) if want_per_plane else None
+    check(lib().dcvic_msssim_loss_f32(_p(real), _p(fake), N, Cc, H, W, float(scale), _p(loss), _p(per), _p(df), _p(ws), ws.numel() * 8, _stream()),
+          "ms_ssim_loss")
+    return loss, df, per
+
+
+def abs_err(a: Tensor, b: Tensor, scale: float, want_grad: bool = True):
+    """scale * sum |a - b| (dcvic_abs_err_f32): (loss: fp64 [1], da = scale * sign(a - b) or None); a, b [N, ...]."""
+    _image_pair("abs_err", a, b)
+    N = a.shape[0] if a.dim() > 0 else 0
+    M = a.numel() // max(N, 1)
+    need = int(lib().dcvic_abs_err_workspace_bytes(N, M))
+    ws = _workspace((need + 7) // 8, a.device, "abs_err", torch.float64)
+    loss = torch.empty(1, dtype=torch.float64, device=a.device)
+    da = torch.empty_like(a) if want_grad else None
+    check(lib().dcvic_abs_err_f32(_p(a), _p(b), M, N, float(scale), _p(loss), _p(da), _p(ws), ws.numel() * 8, _stream()), "abs_err")
+    return loss, da
 
 
 # ------------------------------------------------------------------------------------------- the rate term (csrc/rate_train.hip)

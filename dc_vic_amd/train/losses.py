@@ -145,6 +145,33 @@ def _only(entry: dict, name: str, allowed) -> None:
             _refuse(f"{name}.{k}", entry[k], f"is not a keyword of {entry.get('type')} that is built (known: {', '.join(allowed)})")
 
 
+# distortion_loss types (distortion_loss.py) beside MSELoss: honoured under a rate-distortion trainer only (train/rd_trainer.py)
+RD_DISTORTIONS = ("L1Loss", "MSSSIMLoss")
+
+
+def read_distortion_loss(opt) -> Dict[str, Any]:
+    """dict(type, loss_weight) of `opt['loss']['distortion_loss']` for the rate-distortion trainer: `type` is MSELoss (also when the
+    entry or its type is absent), L1Loss or MSSSIMLoss; `loss_weight` is None when the YAML gives none.  L1Loss and MSSSIMLoss take
+    `loss_weight` only (distortion_loss.py:52-76); another keyword, like another type, is SystemExit with the YAML key and the value.
+    MSELoss's own keywords are judged by read_loss_section."""
+    try:
+        e = dict(opt["loss"]["distortion_loss"] or {})
+    except (KeyError, TypeError):
+        e = {}
+    t = e.get("type")
+    if t in RD_DISTORTIONS:
+        _only(e, "distortion_loss", ("type", "loss_weight"))
+    elif t not in (None, "MSELoss"):
+        _refuse("distortion_loss.type", t, f"is not built, expected MSELoss, {' or '.join(RD_DISTORTIONS)}")
+    w = e.get("loss_weight")
+    if w is not None:
+        try:
+            w = float(w)
+        except (TypeError, ValueError):
+            _refuse("distortion_loss.loss_weight", w, "is not a number")
+    return dict(type=t or "MSELoss", loss_weight=w)
+
+
 def read_loss_section(opt) -> Dict[str, Any]:
     """What the GAN-stage trainers need from `opt['loss']`, or SystemExit naming the YAML key and the value.  An absent entry or an
     absent `type` keeps the trainer's defaults (CrossEntropyLoss, MSELoss on [0, 1], VanillaMSELoss mean, LPIPS alex).  Returns
@@ -155,6 +182,8 @@ def read_loss_section(opt) -> Dict[str, Any]:
       per_sample           True when `trainer.type` names a rate-distortion trainer (its `reduction: none` entries are kept as read)
       line                 the `[train] losses:` log text
       rate                 under a rate-distortion trainer dict(loss_weight or None, reduction) of `rate_loss`, else None
+      distortion_type      MSELoss, or -- under a rate-distortion trainer only -- L1Loss or MSSSIMLoss (read_distortion_loss); the
+                           factor is then 1: it belongs to MSELoss
     `gan_loss` is judged by scripts/train.py's choose_gan_trainer; only its weight is read here."""
     try:
         loss = opt["loss"]
@@ -228,8 +257,12 @@ def read_loss_section(opt) -> Dict[str, Any]:
 
     # distortion_loss
     e = entries.get("distortion_loss", {})
-    factor, d_desc = 0.25, "MSELoss on [0, 1]"
-    if e.get("type") == "MSELoss":
+    factor, d_desc, d_type = 0.25, "MSELoss on [0, 1]", "MSELoss"
+    if per_sample and e.get("type") in RD_DISTORTIONS:
+        d_type = read_distortion_loss(opt)["type"]
+        factor = 1.0
+        d_desc = f"{d_type} on [-1, 1]" + (" (MS_SSIM data_range=1)" if d_type == "MSSSIMLoss" else "")
+    elif e.get("type") == "MSELoss":
         _only(e, "distortion_loss", ("type", "loss_weight", "normalize_img", "mse_scale"))
         norm, scale = e.get("normalize_img", False), e.get("mse_scale", "0_255")
         if not isinstance(norm, bool):
@@ -266,7 +299,7 @@ def read_loss_section(opt) -> Dict[str, Any]:
     line = (f"distortion {d_desc} factor {factor:g}; perceptual LPIPSLoss(net=alex); code_distortion VanillaMSELoss({cd_red}); "
             f"code_ce {ce_desc}")
     return dict(weights=weights, code_ce=code_ce, distortion_factor=factor, code_distortion_reduction=cd_red, per_sample=per_sample, line=line,
-                rate=rate)
+                rate=rate, distortion_type=d_type)
 
 
 def build_code_ce_loss(code_ce: Dict[str, Any], loss_weight: float):

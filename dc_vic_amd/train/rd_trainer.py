@@ -34,6 +34,7 @@ Tensor = torch.Tensor
 # config/exp1_stage1_2.yaml's loss_weight values
 DEFAULT_RD_LOSS = dict(rate=0.5, distortion=50.0, perceptual=1.0, code_distortion=0.006, code_ce=0.003)
 BETA_POLICIES = ("linear", "exp")
+DISTORTION_TYPES = ("MSELoss", "L1Loss", "MSSSIMLoss")
 LOG_KEYS = ("rate", "distortion", "perceptual", "code_distortion", "code_ce", "total", "qbpp", "vq_acc", "lr", "aux")
 
 
@@ -58,10 +59,13 @@ class DualBetaCondRateDistortionVqCodeTrainer(BetaPairTrainerBase):
                  clip_max_norm: Optional[float] = 1.0, loss_weights: Optional[Dict[str, float]] = None, beta_policy: str = "linear",
                  beta_offset: float = 1.0, sample_beta_batch: bool = False, dist=None, seed: int = 0, lpips_state: Optional[Dict[str, Tensor]] = None,
                  rate_reduction: str = "mean", code_ce_gamma: float = 0.0, code_ce_reduction: str = "mean", code_distortion_reduction: str = "mean",
-                 distortion_factor: float = 0.25, gumbel_sampling: bool = False):
+                 distortion_factor: float = 0.25, gumbel_sampling: bool = False, distortion_type: str = "MSELoss"):
         """`loss_weights`: {rate, distortion, perceptual, code_distortion, code_ce} over DEFAULT_RD_LOSS; the three `*_reduction`s are
         none, mean or sum (RateLoss, FocalCrossEntropyLoss, VanillaMSELoss); `code_ce_gamma` 0 is the plain cross entropy;
-        `beta_policy` / `beta_offset` / `sample_beta_batch` default as the reference's constructor does."""
+        `beta_policy` / `beta_offset` / `sample_beta_batch` default as the reference's constructor does; `distortion_type` is MSELoss,
+        L1Loss or MSSSIMLoss (distortion_loss.py), `distortion_factor` belongs to MSELoss alone."""
+        if distortion_type not in DISTORTION_TYPES:
+            raise ValueError(f"distortion_type: {distortion_type} is unknown, expected {', '.join(DISTORTION_TYPES)}")
         if gumbel_sampling:
             raise ValueError("model.gumbel_sampling: true is not built (the Gumbel-softmax sampling of the VQ indices in training mode): set it to false")
         if beta_policy not in BETA_POLICIES:
@@ -83,6 +87,7 @@ class DualBetaCondRateDistortionVqCodeTrainer(BetaPairTrainerBase):
         self.rate_loss = RateLoss(self.w["rate"], reduction=rate_reduction)
         self.code_ce_gamma, self.code_ce_reduction = check_focal_gamma(code_ce_gamma), code_ce_reduction
         self.code_distortion_reduction, self.distortion_factor = code_distortion_reduction, float(distortion_factor)
+        self.distortion_type = distortion_type
         self.beta_policy, self.beta_offset, self.sample_beta_batch = beta_policy, float(beta_offset), bool(sample_beta_batch)
         self.last_beta_rate: Optional[Tensor] = None
         self.last_beta_vq: Optional[Tensor] = None
@@ -139,7 +144,12 @@ class DualBetaCondRateDistortionVqCodeTrainer(BetaPairTrainerBase):
         fake = nets.fusion_decode(ctx, m.fusion_module, m.vq_model.decoder, A.const(lat), feats, w=1.0)
         gt_lat, gt_idx = out["gt_vq_latent"], out["gt_vq_indices"]
         L = {"rate": out["loss"]}
-        L["distortion"] = A.mse_loss(ctx, fake, x, self.w["distortion"] * self.distortion_factor)
+        if self.distortion_type == "MSSSIMLoss":           # raises, naming the size, when min(H, W) <= 160
+            L["distortion"] = A.ms_ssim_loss(ctx, fake, x, self.w["distortion"])
+        elif self.distortion_type == "L1Loss":
+            L["distortion"] = A.l1_loss(ctx, fake, x, self.w["distortion"])
+        else:
+            L["distortion"] = A.mse_loss(ctx, fake, x, self.w["distortion"] * self.distortion_factor)
         if self.lpips is not None:
             from .lpips import lpips_loss
             L["perceptual"] = lpips_loss(ctx, self.lpips, x, fake, self.w["perceptual"])

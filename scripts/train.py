@@ -14,7 +14,8 @@ or seeded synthetic tensors.  Checkpoints use the reference's file format: `comp
 The optimizer / loss settings are the YAML's `optim` / `loss` sections when present (config/exp1_stage1_3.yaml:43-79), else
 their stage-3 values (g_scheduler and d_scheduler milestones are read separately).  Every `loss` entry's `type` and keywords are
 honoured or refused before any GPU work (dc_vic_amd/train/losses.py read_loss_section: CrossEntropyLoss / FocalCrossEntropyLoss,
-MSELoss normalize_img / mse_scale, VanillaMSELoss reduction, LPIPSLoss alex); rank 0 prints them as `[train] losses: ...`.
+MSELoss normalize_img / mse_scale, VanillaMSELoss reduction, LPIPSLoss alex; under the rate-distortion trainer also the distortions
+L1Loss and MSSSIMLoss, csrc/msssim_loss.hip, on crops with min(H, W) > 160); rank 0 prints them as `[train] losses: ...`.
 Without `model.use_selected_beta_pairs` (config/exp1_stage1_3.yaml) beta_rate and beta_vq are drawn per sample from the
 (num_beta_levels + 1)-point grids; `trainer.beta_policy` / `trainer.beta_offset` are read by no GAN trainer of the reference and ignored there.  LPIPS: pass --lpips_path (a torch.save'd state
 dict of lpips.LPIPS(net='alex'), loaded with weights_only=True); its weights cannot be fetched offline, so without it a positive
@@ -175,11 +176,12 @@ def build_rd_trainer(opt, losses, model, dist, seed, lpips_state):
         model, lr=float(_get(opt, "optim", "g_optimizer", "lr", default=1e-4)), aux_lr=float(_get(opt, "optim", "aux_optimizer", "lr", default=1e-3)),
         milestones=list(_get(opt, "optim", "g_scheduler", "milestones", default=[300000])), gamma=float(_get(opt, "optim", "g_scheduler", "gamma", default=0.1)),
         clip_max_norm=_get(opt, "optim", "clip_max_norm", default=1.0), loss_weights=lw, dist=dist, seed=seed, lpips_state=lpips_state,
-        distortion_factor=losses["distortion_factor"], gumbel_sampling=bool(_get(opt, "model", "gumbel_sampling", default=False)), **kw)
+        distortion_factor=losses["distortion_factor"], distortion_type=losses["distortion_type"],
+        gumbel_sampling=bool(_get(opt, "model", "gumbel_sampling", default=False)), **kw)
     line = (f"rate-distortion trainer: {RD_TRAINER}; beta_policy {kw['beta_policy']}" + (f" (offset {kw['beta_offset']:g})" if kw["beta_policy"] == "linear" else "")
             + f", sample_beta_batch {kw['sample_beta_batch']}; weights " + ", ".join(f"{k} {trainer.w[k]:g}" for k in DEFAULT_RD_LOSS)
             + f"; reductions rate {kw['rate_reduction']}, code_distortion {kw['code_distortion_reduction']}, code_ce {kw['code_ce_reduction']}"
-            + f" (gamma {kw['code_ce_gamma']:g})")
+            + f" (gamma {kw['code_ce_gamma']:g}); distortion {trainer.distortion_type}")
     return trainer, line
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """samples/s of the stage-3 training step (BASELINE config 5: 256x256 crops, batch 8 per GPU, G + D step) -- a SEPARATE metric,
-never mixed into bench.py's headline.  python tools/train_bench.py [--gan {vanilla,oasis} | --stage 1_2] [--batch 8] [--steps 5] [--warmup 2]
+never mixed into bench.py's headline.  python tools/train_bench.py [--gan {vanilla,oasis} | --stage 1_2 [--distortion {MSELoss,L1Loss,MSSSIMLoss}]] [--batch 8] [--steps 5] [--warmup 2]
 (--gan oasis: the 257-class per-token discriminator of config/dc_vic_oasis.yaml and the OASIS cross-entropy loss; --stage 1_2: the
 rate-distortion step of train/rd_trainer.py with config/exp1_stage1_2.yaml's trainer and loss sections, no discriminator); under
 torch.distributed.run it is data-parallel (weak scaling) and reports the aggregate."""
@@ -23,6 +23,7 @@ def main():
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--gan", choices=("vanilla", "oasis"), default="vanilla")
     p.add_argument("--stage", choices=("3", "1_2"), default="3", help="3: the G + D step (default); 1_2: the rate-distortion step")
+    p.add_argument("--distortion", choices=("MSELoss", "L1Loss", "MSSSIMLoss"), default="MSELoss", help="--stage 1_2: distortion_loss.type")
     a = p.parse_args()
     rank, world, lr_ = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(lr_)
@@ -38,7 +39,7 @@ def main():
     m = build_comp_model(BaseConfig.fromfile(os.path.join(ROOT, "config", "dc_vic_synthetic.yaml"), {"device": dev}))
     load_synth_weights(m, 1234)
     if a.stage == "1_2":
-        tr, what = rd_trainer(m, dist, rank), "stage 1-2 rate-distortion step"
+        tr, what = rd_trainer(m, dist, rank, a.distortion), "stage 1-2 rate-distortion step" + (f" ({a.distortion})" if a.distortion != "MSELoss" else "")
     else:
         tr, what = gan_trainer(a, m, dev, dist, rank), "stage-3 G+D step"
     g = torch.Generator().manual_seed(100 + rank)
@@ -64,18 +65,20 @@ def main():
         dist.destroy_process_group()
 
 
-def rd_trainer(m, dist, rank):
+def rd_trainer(m, dist, rank, distortion="MSELoss"):
     from dc_vic_amd.train import DualBetaCondRateDistortionVqCodeTrainer
     from dc_vic_amd.train.losses import read_loss_section
     with open(os.path.join(ROOT, "tests", "golden", "reference_loss_sections.json")) as f:
         opt = json.load(f)["exp1_stage1_2.yaml"]
+    if distortion != "MSELoss":
+        opt["loss"]["distortion_loss"] = dict(type=distortion, loss_weight=opt["loss"]["distortion_loss"]["loss_weight"])
     r = read_loss_section(opt)
     lw = {k: v for k, v in r["weights"].items() if k != "gan"}
     lw["rate"] = r["rate"]["loss_weight"]
     return DualBetaCondRateDistortionVqCodeTrainer(
         m, loss_weights=lw, beta_policy=opt["trainer"]["beta_policy"], sample_beta_batch=opt["trainer"]["sample_beta_batch"], dist=dist, seed=rank,
         rate_reduction=r["rate"]["reduction"], code_ce_gamma=r["code_ce"]["gamma"], code_ce_reduction=r["code_ce"]["reduction"],
-        code_distortion_reduction=r["code_distortion_reduction"], distortion_factor=r["distortion_factor"])
+        code_distortion_reduction=r["code_distortion_reduction"], distortion_factor=r["distortion_factor"], distortion_type=r["distortion_type"])
 
 
 def gan_trainer(a, m, dev, dist, rank):

@@ -1,5 +1,5 @@
 """ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h, include/dcvic_rate.h, include/dcvic_train.h, include/dcvic_vq.h,
-include/dcvic_sample_loss.h, include/dcvic_gumbel.h, include/dcvic_msssim_loss.h).  The library is REQUIRED: there is no
+include/dcvic_sample_loss.h, include/dcvic_gumbel.h, include/dcvic_msssim_loss.h, include/dcvic_data.h).  The library is REQUIRED: there is no
 fallback path -- if it is missing or an entry point fails, the caller gets an exception."""
 from __future__ import annotations
 
@@ -132,6 +132,12 @@ MSSSIM_LOSS_SIGNATURES = {
     "dcvic_msssim_loss_workspace_bytes": "q:iiii", "dcvic_msssim_loss_f32": "i:ppiiiidppppqp",
     "dcvic_abs_err_workspace_bytes": "q:iq", "dcvic_abs_err_f32": "i:ppqidpppqp",
 }
+# include/dcvic_data.h: the training data feed's resample / crop / flip / convert launch (csrc/data.hip); dcvic_crop_desc is a struct of
+# 3 long long (src_off, tab_x, tab_y) and 6 int (src_h, src_w, src_stride, flip, kx, ky), passed by address (train/data.py DESC_DTYPE)
+DATA_SIGNATURES = {
+    "dcvic_u8_resample_crop_f32": "i:pqppiippp",
+}
+DATA_MAX_KSIZE = 17
 VQ_NONE, VQ_SHARD, VQ_PACKED2, VQ_PACKED1, VQ_LDS4, VQ_LDS8 = range(6)
 
 _lib = None
@@ -152,7 +158,8 @@ def lib() -> C.CDLL:
             "(or __graft_entry__.build()). dc_vic_amd has no fallback path.")
     L = C.CDLL(LIB_PATH)
     for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items(), *RATE_SIGNATURES.items(), *TRAIN_SIGNATURES.items(), *VQ_SIGNATURES.items(),
-                      *SAMPLE_LOSS_SIGNATURES.items(), *GUMBEL_SIGNATURES.items(), *MSSSIM_LOSS_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
+                      *SAMPLE_LOSS_SIGNATURES.items(), *GUMBEL_SIGNATURES.items(), *MSSSIM_LOSS_SIGNATURES.items(),
+                      *DATA_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
         fn = getattr(L, name)                # AttributeError names a symbol the library lacks
         ret, params = sig.split(":")
         fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[c] for c in params]

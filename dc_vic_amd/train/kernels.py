@@ -1,5 +1,5 @@
 """ctypes wrappers of the training-step kernels (csrc/train.hip, include/dcvic.h "Training step"; csrc/chan_ce.hip; csrc/sample_loss.hip,
-include/dcvic_sample_loss.h; csrc/rate_train.hip, include/dcvic_rate.h; csrc/gumbel.hip, include/dcvic_gumbel.h; csrc/msssim_loss.hip, include/dcvic_msssim_loss.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
+include/dcvic_sample_loss.h; csrc/rate_train.hip, include/dcvic_rate.h; csrc/gumbel.hip, include/dcvic_gumbel.h; csrc/msssim_loss.hip, include/dcvic_msssim_loss.h; csrc/data.hip, include/dcvic_data.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
 from __future__ import annotations
 
 import ctypes
@@ -375,3 +375,21 @@ def resample2(x: Tensor, down: bool) -> Tensor:
         out = torch.empty((N, Cc, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
         check(lib().dcvic_resample2_f32(0, _p(x), _p(out), N * Cc, H, W, _stream()), "resample2")
     return out
+
+
+def u8_resample_crop(slab: Tensor, used: int, desc_host: int, N: int, S: int, table: Tensor, out: Tensor, stream: Optional[int] = None,
+                     desc_off: int = 0) -> None:
+    """The data feed's one launch per batch (csrc/data.hip, include/dcvic_data.h): `slab` a device uint8 tensor whose first `used` bytes
+    hold N dcvic_crop_desc at `desc_off`, the resampling tables and the uint8 source windows (train/data.py slab_layout); `desc_host` the
+    address of the same N descriptors in host memory, on which the entry point makes its checks; `table` the 256 fp32 of the
+    uint8 -> [-1, 1] conversion; `out` [N, 3, S, S] fp32, written whole.  Launches on `stream` (a HIP stream handle), else the current one."""
+    if slab.dtype != torch.uint8 or not slab.is_cuda or not slab.is_contiguous() or not 0 < used <= slab.numel():
+        raise ValueError(f"u8_resample_crop: slab {slab.dtype} {tuple(slab.shape)} {slab.device}, used {used}")
+    if table.dtype != torch.float32 or table.numel() != 256 or not table.is_contiguous() or table.device != slab.device:
+        raise ValueError(f"u8_resample_crop: table {table.dtype} {tuple(table.shape)} {table.device}")
+    if out.dtype != torch.float32 or tuple(out.shape) != (N, 3, S, S) or not out.is_contiguous() or out.device != slab.device:
+        raise ValueError(f"u8_resample_crop: out {out.dtype} {tuple(out.shape)} {out.device}, expected ({N}, 3, {S}, {S}) fp32 on {slab.device}")
+    if slab.device.index != torch.cuda.current_device():
+        raise ValueError(f"u8_resample_crop: slab lives on {slab.device} but the current HIP device is cuda:{torch.cuda.current_device()}")
+    check(lib().dcvic_u8_resample_crop_f32(_p(slab), int(used), _p(slab) + int(desc_off), int(desc_host), N, S, _p(table), _p(out),
+                                           _stream() if stream is None else stream), "u8_resample_crop")

@@ -4,12 +4,20 @@ src/trainer/base_trainer.py:130-152 (train_loop) for the `DualBetaCondGanDistort
 
     python scripts/train.py CONFIG [--model_path CKPT | --synthetic_weights] [--dataset_root DIR | --synthetic_data]
                             [--batch_size 8] [--total_iter N] [--save_dir DIR] [--save_step N] [--seed S] [-d cuda:0]
+                            [--data_workers N] [--data_depth 2]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train.py ...
 
 One process per GPU; every rank draws its own crops (sampler sharded by rank), gradients are averaged with bucketed RCCL
 all-reduces of the flat gradient buffers (the reference is single-GPU, README.md:64-65).  Data: PNG / JPG files under
 --dataset_root -> RandomCrop 256 (reflect pad if smaller) -> horizontal flip -> [-1, 1] (src/dataset/data_transform.py:19-45),
-or seeded synthetic tensors.  Checkpoints use the reference's file format: `comp_model_iterXXXXXXX.pth.tar` =
+or seeded synthetic tensors.  The real-data stream is dc_vic_amd/train/data.py's: CropPlanner states it from the seed and the image
+headers (without resize it is CropDataset's below, bit for bit), --data_workers threads decode --data_depth batches ahead, the crop's
+source window travels as uint8 through pinned memory and one HIP launch per batch (csrc/data.hip) does Pillow's 8-bit resampling, the
+flip, the [-1, 1] conversion and the NCHW layout; --data_workers 0 runs the same stream serially on the host (equal bits).  The YAML's
+`dataset.train_dataset` section is honoured or refused before any GPU work (read_train_dataset: image_size 256, resize_range [f_min, f_max]
+with interpolation bicubic / bilinear = the reference's PilRandomResize, root_dir and subset_list = its root_dir/train_{k}/*.jpg layout,
+used when --dataset_root is absent or holds only train_{k} folders); `dataset.batch_size` is reported, --batch_size decides; rank 0 prints
+`[train] data: ...`.  --resume replays the plan's draws, so a resumed run sees the batches of the uninterrupted one.  Checkpoints use the reference's file format: `comp_model_iterXXXXXXX.pth.tar` =
 {'iter', 'comp_model': state_dict}, `discriminator_iter...` = {'iter', 'discriminator': state_dict} (model_saver.py:39-46).
 The optimizer / loss settings are the YAML's `optim` / `loss` sections when present (config/exp1_stage1_3.yaml:43-79), else
 their stage-3 values (g_scheduler and d_scheduler milestones are read separately).  Every `loss` entry's `type` and keywords are
@@ -57,6 +65,7 @@ from dc_vic_amd import BaseConfig, build_comp_model  # noqa: E402
 from dc_vic_amd.parallel import launched_by_a_launcher, pin_rank_cpus, self_launch  # noqa: E402
 from dc_vic_amd.registry import TRAINER_REGISTRY  # noqa: E402
 from dc_vic_amd.train import DualBetaCondTamingNLayerDiscriminator  # noqa: E402  (registers both stage-3 trainers)
+from dc_vic_amd.train.data import HostFeed, TrainFeed, list_train_images, read_train_dataset  # noqa: E402
 from dc_vic_amd.train.losses import build_code_ce_loss, read_loss_section  # noqa: E402
 from dc_vic_amd.train.validation import EvalCSV, eval_image_paths, load_eval_images  # noqa: E402
 
@@ -221,6 +230,61 @@ class CropDataset:
         return out
 
 
+def list_training_set(a, opt):
+    """The training images of a run, before any GPU work (pure host: the YAML's `dataset` section and a directory listing) ->
+    None for --synthetic_data, else dict(paths, root, layout "flat" | "subsets", section = read_train_dataset's dict).  --dataset_root DIR
+    is listed flat (sorted png / jpg / jpeg, as CropDataset lists it); if DIR holds no image at its top level but the `train_{k}`
+    folders of the YAML's subset_list, it is read by subsets (openimage_dataset.py:14-34).  Without --dataset_root the YAML's
+    dataset.train_dataset.root_dir is used, by subsets when the YAML names a subset_list.  SystemExit names the key and value the
+    section is refused for, a missing folder and an empty listing."""
+    if a.synthetic_data:
+        return None
+    try:
+        sec = read_train_dataset(opt, threaded=a.data_workers != 0)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    root, src = (a.dataset_root, "--dataset_root") if a.dataset_root else (sec["root_dir"], "dataset.train_dataset.root_dir")
+    if not root:
+        raise SystemExit("no training data: pass --dataset_root DIR or --synthetic_data, or set dataset.train_dataset.root_dir in the YAML")
+    if not os.path.isdir(root):
+        raise SystemExit(f'{src}: folder "{root}" does not exist')
+    sub = sec["subset_list"]
+    try:
+        if a.dataset_root:
+            paths, layout = list_train_images(root), "flat"
+            if not paths and sub and any(os.path.isdir(os.path.join(root, f"train_{k}")) for k in sub):
+                paths, layout = list_train_images(root, sub), "subsets"
+        else:
+            paths, layout = (list_train_images(root, sub), "subsets") if sub else (list_train_images(root), "flat")
+    except ValueError as e:
+        raise SystemExit(f"{src}: {e}")
+    if not paths:
+        raise SystemExit(f'{src}: folder "{root}" holds no image ({"train_{k}/*.jpg of subset_list " + str(sub) if layout == "subsets" else "*.png, *.jpg, *.jpeg"})')
+    return dict(paths=paths, root=root, layout=layout, section=sec)
+
+
+def build_train_data(a, opt, rank, world, device, listing=None):
+    """(feed, log line) of a run's real-data stream, (None, None) for --synthetic_data: TrainFeed (decode threads, pinned uint8, one HIP
+    launch per batch) or, with --data_workers 0, HostFeed (serial, on the host).  Both serve the stream of CropPlanner, which without
+    resize_range is CropDataset's bit for bit.  `listing`: list_training_set's answer when the caller already has it."""
+    listing = list_training_set(a, opt) if listing is None else listing
+    if listing is None:
+        return None, None
+    sec = listing["section"]
+    kw = dict(resize_range=sec["resize_range"], interpolation=sec["interpolation"])
+    if a.data_workers == 0:
+        feed, how = HostFeed(listing["paths"], 256, rank, world, a.seed, **kw), "serial on the host (--data_workers 0)"
+    else:
+        feed = TrainFeed(listing["paths"], 256, rank, world, a.seed, device, workers=a.data_workers, depth=a.data_depth, **kw)
+        how = f"{feed.workers} decode threads, depth {feed.depth}"
+    rr = sec["resize_range"]
+    line = (f"data: {len(listing['paths'])} images under \"{listing['root']}\" ({'flat' if listing['layout'] == 'flat' else 'by subsets ' + str(sec['subset_list'])}); "
+            f"crop 256; resize " + ("off" if rr is None else f"[{rr[0]:g}, {rr[1]:g}] {sec['interpolation']}") + f"; {how}"
+            + (f"; the YAML's dataset.batch_size {sec['batch_size']} is not used, --batch_size {a.batch_size} decides"
+               if sec["batch_size"] is not None and sec["batch_size"] != a.batch_size else ""))
+    return feed, line
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("config_path", type=str)
@@ -242,11 +306,16 @@ def main():
     p.add_argument("--eval_dataset_root", type=str, default=None, help="folder of eval PNGs (overrides the YAML's dataset.eval_dataset.root_dir)")
     p.add_argument("-e", "--eval_step", type=int, default=None, help="validate every N iterations (overrides the YAML's eval_step; 0 = off)")
     p.add_argument("--gan", choices=("vanilla", "oasis"), default=None, help="GAN loss / trainer (default: from the YAML, see choose_gan_trainer)")
+    p.add_argument("--data_workers", type=int, default=None, help="image decode threads of this rank (default: min(8, its share of the cores)); 0 = the serial host path")
+    p.add_argument("--data_depth", type=int, default=2, help="batches decoded ahead of the trainer")
     a = p.parse_args()
+    if (a.data_workers is not None and a.data_workers < 0) or a.data_depth < 1:
+        raise SystemExit(f"--data_workers {a.data_workers} / --data_depth {a.data_depth}: need workers >= 0 and depth >= 1")
     opt0 = BaseConfig.fromfile(a.config_path, {"is_train": True})
     gan_kind, trainer_name, gan_reason = choose_trainer(opt0, a.gan)       # before any GPU work
     losses = read_loss_section(opt0)                                       # likewise: every `loss` entry is honoured or refused
     gumbel_on, gumbel_tau_ = read_gumbel_options(opt0) if gan_kind != "rd" else (False, 1.0)    # likewise
+    listing = list_training_set(a, opt0)                                   # likewise: the `dataset` section, the folder, its listing
     if a.eval_dataset_root is not None:
         try:                                          # a folder named on the command line must hold PNGs: checked before any GPU work
             eval_image_paths(a.eval_dataset_root)
@@ -357,41 +426,49 @@ def main():
         if a.resume:                                  # base_trainer.py: the job's CSV is loaded and extended
             prev = path if os.path.exists(path) else os.path.join(os.path.dirname(a.resume), "eval_result.csv")
         eval_csv = EvalCSV(path, resume_from=prev, start_iter=start_iter)
-    data = None if a.synthetic_data else CropDataset(a.dataset_root, 256, rank, world, a.seed)
     gen = torch.Generator().manual_seed(a.seed * 7919 + rank)
     if a.save_dir and rank == 0:
         os.makedirs(a.save_dir, exist_ok=True)
-    if data is None:
-        for _ in range(start_iter):          # resume: the synthetic stream continues where the interrupted run stopped
-            torch.rand((a.batch_size, 3, 256, 256), generator=gen)
-    t0 = time.perf_counter()
-    t_eval = 0.0                                      # time spent in validation (and at its barrier): not training throughput
-    for it in range(start_iter + 1, total_iter + 1):
-        x = (torch.rand((a.batch_size, 3, 256, 256), generator=gen) * 2 - 1) if data is None else data.batch(a.batch_size)
-        log = trainer.optimize_parameters(it, {"real_images": x})
-        if rank == 0 and (it % a.log_step == 0 or it == 1 or it == total_iter):
-            dt = time.perf_counter() - t0 - t_eval
-            msg = "skipped (loss anomaly)" if log is None else " ".join(f"{k} {v:.5g}" for k, v in log.items())
-            print(f"iter {it:7d} | {world * a.batch_size * (it - start_iter) / dt:7.2f} samples/s | {msg}", flush=True)
-        if do_eval and it % eval_step == 0:
-            tv = time.perf_counter()
-            if rank == 0:
-                res = trainer.validation(it, eval_images)
-                # base_trainer.py:178-192: the log lines, then the CSV row
-                print(f"validation iter{it} ({time.perf_counter() - tv:.2f} s)\n" + "".join(f"\t {k}: {v:.4f}\n" for k, v in res.items()),
-                      end="", flush=True)
-                if eval_csv is not None:
-                    eval_csv.append({"iter": it, **res})
-            if dist is not None:
-                dist.barrier()
-            t_eval += time.perf_counter() - tv
-        if a.save_dir and a.save_step and it % a.save_step == 0 and rank == 0:
-            torch.save({"iter": it, "comp_model": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}},
-                       os.path.join(a.save_dir, f"comp_model_iter{it:07d}.pth.tar"))
-            if not is_rd:
-                torch.save({"iter": it, "discriminator": {k: v.detach().cpu().clone() for k, v in D.state_dict().items()}},
-                           os.path.join(a.save_dir, f"discriminator_iter{it:07d}.pth.tar"))
-            torch.save(trainer.training_state(it), os.path.join(a.save_dir, f"training_state_iter{it:07d}.pth.tar"))
+    data, data_line = build_train_data(a, opt, rank, world, device, listing)
+    try:                                              # the feed's threads are joined on every way out
+        if data_line and rank == 0:
+            print("[train] " + data_line, flush=True)
+        if data is None:
+            for _ in range(start_iter):          # resume: the synthetic stream continues where the interrupted run stopped
+                torch.rand((a.batch_size, 3, 256, 256), generator=gen)
+        else:
+            data.skip(start_iter * a.batch_size)  # likewise the real one: the plan replays its draws from the image headers
+        t0 = time.perf_counter()
+        t_eval = 0.0                                      # time spent in validation (and at its barrier): not training throughput
+        for it in range(start_iter + 1, total_iter + 1):
+            x = (torch.rand((a.batch_size, 3, 256, 256), generator=gen) * 2 - 1) if data is None else data.batch(a.batch_size)
+            log = trainer.optimize_parameters(it, {"real_images": x})
+            if rank == 0 and (it % a.log_step == 0 or it == 1 or it == total_iter):
+                dt = time.perf_counter() - t0 - t_eval
+                msg = "skipped (loss anomaly)" if log is None else " ".join(f"{k} {v:.5g}" for k, v in log.items())
+                print(f"iter {it:7d} | {world * a.batch_size * (it - start_iter) / dt:7.2f} samples/s | {msg}", flush=True)
+            if do_eval and it % eval_step == 0:
+                tv = time.perf_counter()
+                if rank == 0:
+                    res = trainer.validation(it, eval_images)
+                    # base_trainer.py:178-192: the log lines, then the CSV row
+                    print(f"validation iter{it} ({time.perf_counter() - tv:.2f} s)\n" + "".join(f"\t {k}: {v:.4f}\n" for k, v in res.items()),
+                          end="", flush=True)
+                    if eval_csv is not None:
+                        eval_csv.append({"iter": it, **res})
+                if dist is not None:
+                    dist.barrier()
+                t_eval += time.perf_counter() - tv
+            if a.save_dir and a.save_step and it % a.save_step == 0 and rank == 0:
+                torch.save({"iter": it, "comp_model": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}},
+                           os.path.join(a.save_dir, f"comp_model_iter{it:07d}.pth.tar"))
+                if not is_rd:
+                    torch.save({"iter": it, "discriminator": {k: v.detach().cpu().clone() for k, v in D.state_dict().items()}},
+                               os.path.join(a.save_dir, f"discriminator_iter{it:07d}.pth.tar"))
+                torch.save(trainer.training_state(it), os.path.join(a.save_dir, f"training_state_iter{it:07d}.pth.tar"))
+    finally:
+        if data is not None:
+            data.close()
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

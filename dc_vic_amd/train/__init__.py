@@ -3,7 +3,8 @@ optimizer kernels (csrc/train.hip via kernels.py), differentiable forwards of th
 discriminator (nets.py) and the stage-3 GAN trainers (PatchGAN / BCE and OASIS / per-token cross entropy, csrc/chan_ce.hip) with
 data-parallel gradient averaging (trainer.py); the stage 1-2 rate-distortion trainer with per-sample beta weights (rd_trainer.py,
 csrc/sample_loss.hip); the code losses of the YAML's `loss` section (plain and focal cross entropy,
-csrc/chan_ce.hip) and its host-side reading (losses.py); the real-data feed (data.py: the seeded crop plan, Pillow's 8-bit resampling
+csrc/chan_ce.hip) and its host-side reading (losses.py); the choice and construction of the trainer a config asks for (build.py:
+choose_trainer, rd_trainer_kwargs / gan_trainer_kwargs, build_trainer); the real-data feed (data.py: the seeded crop plan, Pillow's 8-bit resampling
 restated, decode threads, pinned uint8 staging and the one launch of csrc/data.hip per batch)."""
 from .autograd import Ctx, ParamGroup, Var  # noqa: F401
 from .nets import DualBetaCondTamingNLayerDiscriminator  # noqa: F401

@@ -121,6 +121,10 @@ class Ctx:
             fn()
         self.tape = []
 
+    def discard(self) -> None:
+        """Forget the recorded pass without running it (a skipped step): the entries and what they hold are released."""
+        self.tape = []
+
 
 def acc(v: Var, g: Tensor) -> None:
     """v.grad += g (out of place: a gradient tensor may be shared by several consumers)."""

@@ -1,0 +1,170 @@
+"""The trainer a parsed config asks for: which one (choose_trainer, choose_gan_trainer, read_gumbel_options), the constructors' keyword
+arguments from the YAML's `trainer` / `optim` / `loss` / `model` sections (rd_trainer_kwargs, gan_trainer_kwargs: pure, no GPU, no model)
+and the built trainer with its `[train]` log lines (build_trainer): one place for scripts/train.py, the benchmarks under tools/ and the tests."""
+from __future__ import annotations
+
+from typing import Any, Dict, List, Optional, Tuple
+
+from ..registry import TRAINER_REGISTRY
+from .losses import build_code_ce_loss
+from .rd_trainer import DEFAULT_RD_LOSS
+from .trainer import DEFAULT_LOSS, gumbel_tau
+
+
+def get_in(d, *keys, default=None):
+    for k in keys:
+        try:
+            d = d[k]
+        except (KeyError, TypeError):
+            return default
+    return d
+
+
+VANILLA_TRAINER, OASIS_TRAINER = "DualBetaCondGanDistortionVqCodeTrainer", "DualBetaCondOasisGanDistortionVqFusionTrainer"
+_TRAINER_KIND = {VANILLA_TRAINER: "vanilla", OASIS_TRAINER: "oasis"}
+_LOSS_KIND = {"VanillaGANLoss": "vanilla", "OasisGANLoss": "oasis"}
+RD_TRAINER, RD_STAGE_1_1 = "DualBetaCondRateDistortionVqCodeTrainer", "RateDistortionVqCodeTrainer"
+# the discriminator of a config without a `discriminator` section: the stage-3 PatchGAN
+DEFAULT_DISCRIMINATOR = dict(type="DualBetaCondTamingNLayerDiscriminator", input_nc=11, n_layers=3, ndf=64, norm_type="none", max_beta_1=3.0,
+                             max_beta_2=3.5, L=10, cond_ch=8, use_pi=False, include_x=True)
+
+
+def choose_gan_trainer(opt, gan_flag=None):
+    """(kind, trainer class name, reason) for a parsed config (pure: no GPU, no model).  Order: the --gan flag; `trainer.type`;
+    `loss.gan_loss.type`; the discriminator's `out_nc` (absent or 1 -> vanilla, n_embed + 1 -> oasis).  SystemExit for an unknown
+    type, for `trainer.mc_sampling` (not built) and for a choice the discriminator cannot serve: OASIS needs out_nc = n_embed + 1
+    of the VQ codebook and keep_shape (one 257-way classification per token), the BCE PatchGAN must not get that discriminator."""
+    n_embed = get_in(opt, "subnet", "vq_model", "n_embed")
+    out_nc = int(get_in(opt, "discriminator", "out_nc", default=1))
+    keep_shape = bool(get_in(opt, "discriminator", "keep_shape", default=False))
+    if get_in(opt, "trainer", "mc_sampling", default=False):
+        raise SystemExit("trainer.mc_sampling: true is not built (the reference's split of a batch into a generator half and a discriminator "
+                         "half with dataset-supplied VQ indices): set it to false")
+    t_type, l_type = get_in(opt, "trainer", "type"), get_in(opt, "loss", "gan_loss", "type")
+    if gan_flag is not None:
+        if gan_flag not in ("vanilla", "oasis"):
+            raise SystemExit(f"--gan {gan_flag}: unknown, expected vanilla or oasis")
+        kind, reason = gan_flag, f"--gan {gan_flag}"
+    elif t_type is not None:
+        if t_type not in _TRAINER_KIND:
+            raise SystemExit(f"trainer.type: {t_type} is unknown, expected {VANILLA_TRAINER} or {OASIS_TRAINER}")
+        kind, reason = _TRAINER_KIND[t_type], f"trainer.type: {t_type}"
+    elif l_type is not None:
+        if l_type not in _LOSS_KIND:
+            raise SystemExit(f"loss.gan_loss.type: {l_type} is unknown, expected VanillaGANLoss or OasisGANLoss")
+        kind, reason = _LOSS_KIND[l_type], f"loss.gan_loss.type: {l_type}"
+    elif out_nc == 1:
+        kind, reason = "vanilla", "discriminator.out_nc: 1"
+    elif n_embed is not None and out_nc == int(n_embed) + 1:
+        kind, reason = "oasis", f"discriminator.out_nc: {out_nc} = n_embed + 1"
+    else:
+        raise SystemExit(f"discriminator.out_nc: {out_nc} names no GAN loss (1 -> vanilla, n_embed + 1 = "
+                         f"{'?' if n_embed is None else int(n_embed) + 1} -> oasis) and neither --gan, trainer.type nor loss.gan_loss.type is given")
+    if gan_flag is None and t_type in _TRAINER_KIND and l_type in _LOSS_KIND and _TRAINER_KIND[t_type] != _LOSS_KIND[l_type]:
+        raise SystemExit(f"trainer.type: {t_type} cannot train with loss.gan_loss.type: {l_type}")
+    if kind == "oasis":
+        if n_embed is None:
+            raise SystemExit(f"OASIS GAN loss ({reason}) needs subnet.vq_model.n_embed to size the discriminator's classes")
+        if out_nc != int(n_embed) + 1:
+            raise SystemExit(f"OASIS GAN loss ({reason}) cannot train a discriminator with out_nc: {out_nc}; it needs n_embed + 1 = {int(n_embed) + 1}")
+        if not keep_shape:
+            raise SystemExit(f"OASIS GAN loss ({reason}) cannot train a discriminator with keep_shape: false; its logits must lie on the VQ token grid")
+    elif n_embed is not None and out_nc == int(n_embed) + 1 and out_nc != 1:
+        raise SystemExit(f"vanilla GAN loss ({reason}) cannot train a discriminator with out_nc: {out_nc} (n_embed + 1 classes: an OASIS "
+                         "discriminator); use --gan oasis or out_nc: 1")
+    return kind, (OASIS_TRAINER if kind == "oasis" else VANILLA_TRAINER), reason
+
+
+def read_gumbel_options(opt):
+    """(gumbel_sampling, tau) of a parsed config's `model` section for the GAN-stage trainers (pure: no GPU, no model), called after
+    choose_gan_trainer.  `model.gumbel_kwargs` may hold `tau` (a number > 0, default 1) and nothing else: the sample is the reference's
+    F.gumbel_softmax(logits, dim=1, hard=True, **gumbel_kwargs), so `hard` and `dim` would raise there and `eps` does nothing.
+    SystemExit names the key and its value.  The keywords are checked with the option off too, as the model's constructor takes them."""
+    kw = get_in(opt, "model", "gumbel_kwargs", default=None)
+    try:
+        tau = gumbel_tau(dict(kw) if kw else None)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    return bool(get_in(opt, "model", "gumbel_sampling", default=False)), tau
+
+
+def choose_trainer(opt, gan_flag=None):
+    """(kind, trainer class name, reason) for a parsed config (pure: no GPU, no model): kind "rd" for the stage 1-2 rate-distortion
+    trainer (`trainer.type: DualBetaCondRateDistortionVqCodeTrainer`), else choose_gan_trainer's answer.  SystemExit for the stage 1-1
+    trainer (not built), for --gan together with a rate-distortion trainer type, and for what that trainer does not build."""
+    t_type = get_in(opt, "trainer", "type")
+    if t_type == RD_STAGE_1_1:
+        raise SystemExit(f"trainer.type: {t_type} (stage 1-1, config/exp1_stage1_1.yaml) is not built: it trains the unconditioned model, which needs "
+                         "HyperpriorCharmVicModel, ElicVqCatScEncoder, ElicFeatFusionDecoder and LinearWarmupScheduler; the dual-conditioned "
+                         f"stage 1-2 trainer {RD_TRAINER} is")
+    if t_type != RD_TRAINER:
+        return choose_gan_trainer(opt, gan_flag)
+    if gan_flag is not None:
+        raise SystemExit(f"--gan {gan_flag} cannot go with trainer.type: {t_type}: the rate-distortion trainer has no discriminator and no GAN loss")
+    if get_in(opt, "model", "gumbel_sampling", default=False):
+        raise SystemExit("model.gumbel_sampling: true is not built (the Gumbel-softmax sampling of the VQ indices in training mode): set it to false")
+    policy = get_in(opt, "trainer", "beta_policy", default="linear")
+    if policy not in ("linear", "exp"):
+        raise SystemExit(f"trainer.beta_policy: {policy} is unknown, expected linear or exp")
+    if get_in(opt, "loss", "gan_loss") is not None:
+        raise SystemExit(f"loss.gan_loss has no place under trainer.type: {t_type}: it trains no GAN loss")
+    return "rd", RD_TRAINER, f"trainer.type: {t_type}"
+
+
+def _optim_kwargs(opt) -> Dict[str, Any]:
+    """What both kinds of trainer read from `optim`: the generator side's schedule and the clip, with the stage-3 values when absent."""
+    return dict(milestones=list(get_in(opt, "optim", "g_scheduler", "milestones", default=[300000])),
+                gamma=float(get_in(opt, "optim", "g_scheduler", "gamma", default=0.1)), clip_max_norm=get_in(opt, "optim", "clip_max_norm", default=1.0))
+
+
+def rd_trainer_kwargs(opt, losses) -> Dict[str, Any]:
+    """The rate-distortion trainer's keyword arguments (all but model, dist, seed, lpips_state) from a parsed config and its read_loss_section."""
+    lw = {k: v for k, v in losses["weights"].items() if k in DEFAULT_RD_LOSS}
+    rate = losses["rate"] or dict(loss_weight=None, reduction="mean")
+    if rate["loss_weight"] is not None:
+        lw["rate"] = rate["loss_weight"]
+    return dict(lr=float(get_in(opt, "optim", "g_optimizer", "lr", default=1e-4)), aux_lr=float(get_in(opt, "optim", "aux_optimizer", "lr", default=1e-3)),
+                **_optim_kwargs(opt), loss_weights=lw, beta_policy=get_in(opt, "trainer", "beta_policy", default="linear"),
+                beta_offset=float(get_in(opt, "trainer", "beta_offset", default=1.0)),
+                sample_beta_batch=bool(get_in(opt, "trainer", "sample_beta_batch", default=False)), rate_reduction=rate["reduction"],
+                code_ce_gamma=losses["code_ce"]["gamma"], code_ce_reduction=losses["code_ce"]["reduction"],
+                code_distortion_reduction=losses["code_distortion_reduction"], distortion_factor=losses["distortion_factor"],
+                distortion_type=losses["distortion_type"], gumbel_sampling=bool(get_in(opt, "model", "gumbel_sampling", default=False)))
+
+
+def gan_trainer_kwargs(opt, losses, gumbel: Tuple[bool, float]) -> Dict[str, Any]:
+    """The GAN-stage trainers' keyword arguments (all but model, discriminator, dist, seed, lpips_state); `gumbel`: read_gumbel_options' pair."""
+    lw = dict(losses["weights"])
+    return dict(lr_g=float(get_in(opt, "optim", "g_optimizer", "lr", default=1e-4)), lr_d=float(get_in(opt, "optim", "d_optimizer", "lr", default=1e-4)),
+                **_optim_kwargs(opt), loss_weights=lw, sample_beta_batch=bool(get_in(opt, "trainer", "sample_beta_batch", default=True)),
+                d_milestones=get_in(opt, "optim", "d_scheduler", "milestones", default=None), d_gamma=get_in(opt, "optim", "d_scheduler", "gamma", default=None),
+                code_ce_loss=build_code_ce_loss(losses["code_ce"], lw.get("code_ce", DEFAULT_LOSS["code_ce"])),
+                distortion_factor=losses["distortion_factor"], code_distortion_reduction=losses["code_distortion_reduction"],
+                gumbel_sampling=gumbel[0], gumbel_kwargs=dict(tau=gumbel[1]))
+
+
+def build_rd_trainer(opt, losses, model, dist, seed, lpips_state):
+    """The rate-distortion trainer from the YAML's `trainer`, `optim` and `loss` sections -> (trainer, the `[train]` log line)."""
+    kw = rd_trainer_kwargs(opt, losses)
+    trainer = TRAINER_REGISTRY.get(RD_TRAINER)(model, dist=dist, seed=seed, lpips_state=lpips_state, **kw)
+    line = (f"rate-distortion trainer: {RD_TRAINER}; beta_policy {kw['beta_policy']}" + (f" (offset {kw['beta_offset']:g})" if kw["beta_policy"] == "linear" else "")
+            + f", sample_beta_batch {kw['sample_beta_batch']}; weights " + ", ".join(f"{k} {trainer.w[k]:g}" for k in DEFAULT_RD_LOSS)
+            + f"; reductions rate {kw['rate_reduction']}, code_distortion {kw['code_distortion_reduction']}, code_ce {kw['code_ce_reduction']}"
+            + f" (gamma {kw['code_ce_gamma']:g}); distortion {trainer.distortion_type}")
+    return trainer, line
+
+
+def build_trainer(opt, losses, model, discriminator, dist, seed, lpips_state, gan_flag: Optional[str] = None) -> Tuple[Any, List[str]]:
+    """The trainer `opt` (with the --gan flag) asks for over `model` and, for a GAN one, `discriminator` -> (trainer, its `[train]` log lines)."""
+    kind, name, reason = choose_trainer(opt, gan_flag)
+    if kind == "rd":
+        trainer, line = build_rd_trainer(opt, losses, model, dist, seed, lpips_state)
+        return trainer, [line, "losses: " + losses["line"]]
+    on, tau = read_gumbel_options(opt)
+    kw = gan_trainer_kwargs(opt, losses, (on, tau))
+    lw = kw["loss_weights"]
+    w_src = "loss.gan_loss.loss_weight" if "gan" in lw else "default, no reference YAML pins it" if kind == "oasis" else "default"
+    lines = [f"GAN trainer: {kind} ({name}), chosen by {reason}; generator-side gan weight {lw.get('gan', DEFAULT_LOSS['gan']):g} ({w_src})",
+             "losses: " + losses["line"] + "; weights " + ", ".join(f"{k} {lw.get(k, v):g}" for k, v in DEFAULT_LOSS.items()),
+             "VQ sampling: " + (f"gumbel-softmax (tau {tau:g})" if on else "argmax")]
+    return TRAINER_REGISTRY.get(name)(model, discriminator, dist=dist, seed=seed, lpips_state=lpips_state, **kw), lines

@@ -317,6 +317,22 @@ def fusion_decode(ctx: Ctx, fm, vq_dec, z: Var, cond_feats: Dict[str, Var], w: f
     return A.conv(ctx, h, vq_dec.conv_out)
 
 
+def synthesis_forward(ctx: Ctx, model, y_hat, beta_rate, beta_vq, gumbel: Optional[Tuple[Tensor, float]] = None) -> Dict:
+    """The synthesis side of a training step, analysis_forward's counterpart (hyperprior_dc_vic_model.py:240-274): decoder features of y_hat
+    (Tensor or Var, see decoder_get_feats), the VQ estimator, its logits' argmax through the post_quant_conv LUT, the fusion decoder.  With
+    `gumbel` = (noise, tau), the caller's draw, the decoder reads the hard Gumbel-softmax sample's latent (:254-260); out_vq_indices stays the argmax."""
+    feat_1, feats = decoder_get_feats(ctx, model.decoder, y_hat, beta_rate, beta_vq)
+    pred_embed, logits = estimator_forward(ctx, model.vq_estimator, feat_1)
+    pq = model.vq_model.post_quant_conv
+    codebook, pq_w = model.vq_model.quantize.embedding.weight, pq.weight.reshape(pq.out_channels, -1).contiguous()
+    out_idx, lat = ops.argmax_lut(logits.data, codebook, pq_w, pq.bias)
+    z = A.const(lat)
+    if gumbel is not None:
+        _, z = A.gumbel_vq_latent(ctx, logits, gumbel[0], codebook, pq_w, pq.bias, gumbel[1])
+    fake = fusion_decode(ctx, model.fusion_module, model.vq_model.decoder, z, feats, w=1.0)
+    return dict(fake=fake, pred_embed=pred_embed, logits=logits, out_vq_indices=out_idx)
+
+
 # ------------------------------------------------------------------------------------------- discriminator
 class DualBetaCondTamingNLayerDiscriminator(nn.Module):
     """PatchGAN conditioned on (beta_rate, beta_vq): state-dict keys `main.{0,2,5,8,11}.{weight,bias}`, `mlp.{0,2}.{weight,bias}`

@@ -7,8 +7,8 @@ the two code losses carry one weight per image, exp(beta) or beta + offset (`app
 train apart, with their own Adam on EntropyBottleneck.loss(), AFTER the main step (`optimize_aux_parameters`).
 
 The step runs on the tape: nets.analysis_forward (encoder, hyperprior, CHARM, both entropy models with uniform noise; the rate term's
-gradients are seeded by csrc/rate_train.hip), then decoder_get_feats on the `Var` y_hat, the estimator, the argmax LUT and the fusion
-decoder, so the image and code losses reach the analysis side through y_hat's straight-through estimator.  The per-image weighting of the
+gradients are seeded by csrc/rate_train.hip), then nets.synthesis_forward on the `Var` y_hat (decoder features, estimator, argmax LUT, fusion
+decoder), so the image and code losses reach the analysis side through y_hat's straight-through estimator; the step's pieces are BetaPairTrainerBase's.  The per-image weighting of the
 code losses is csrc/sample_loss.hip (A.mse_loss_weighted, A.focal_cross_entropy_loss_weighted, losses.sample_loss_weights).
 
 Differences, stated: those of trainer.py (LPIPS weights, data-parallel averaging); the uniform noise comes from a trainer-owned device
@@ -20,14 +20,12 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from .. import ops
 from ..registry import TRAINER_REGISTRY
 from . import autograd as A
-from . import kernels as K
 from . import nets
 from .autograd import Ctx, ParamGroup
 from .losses import RateLoss, check_focal_gamma, sample_loss_weights
-from .trainer import Adam, BetaPairTrainerBase, MultiStepLR, allreduce_mean_, loss_anomaly
+from .trainer import Adam, BetaPairTrainerBase, MultiStepLR, adam_state, load_adam_state
 
 Tensor = torch.Tensor
 
@@ -97,23 +95,13 @@ class DualBetaCondRateDistortionVqCodeTrainer(BetaPairTrainerBase):
         self._build_lpips(self.w["perceptual"], lpips_state, dev)
 
     # ---------------------------------------------------------------- training state
-    def _tagged(self):
-        return (("main", self.group, self.opt), ("aux", self.aux_group, self.aux_opt))
-
     def training_state(self, current_iter: int) -> Dict:
-        st = {"iter": int(current_iter), "rng": self.rng.get_state(), "noise_gen": self.noise_gen.get_state().clone(),
-              "last_epoch": int(self.sched.last_epoch)}
-        for tag, grp, opt_ in self._tagged():
-            st[tag] = {"m": grp.m.detach().cpu().clone(), "v": grp.v.detach().cpu().clone(), "t": int(opt_.t), "numel": int(grp.numel())}
-        return st
+        return {"iter": int(current_iter), "rng": self.rng.get_state(), "noise_gen": self.noise_gen.get_state().clone(),
+                "last_epoch": int(self.sched.last_epoch), "main": adam_state(self.opt), "aux": adam_state(self.aux_opt)}
 
     def load_training_state(self, st: Dict) -> int:
-        for tag, grp, opt_ in self._tagged():
-            s_ = st[tag]
-            if int(s_["numel"]) != grp.numel():
-                raise ValueError(f"training state: {tag} group has {s_['numel']} parameters, this model {grp.numel()}")
-            grp.m.copy_(s_["m"].to(grp.m.device)); grp.v.copy_(s_["v"].to(grp.v.device))
-            opt_.t = int(s_["t"])
+        load_adam_state(self.opt, st["main"], "main")
+        load_adam_state(self.aux_opt, st["aux"], "aux")
         self.sched.last_epoch = int(st["last_epoch"])
         self.rng.set_state(st["rng"])
         self.noise_gen.set_state(st["noise_gen"])
@@ -124,6 +112,10 @@ class DualBetaCondRateDistortionVqCodeTrainer(BetaPairTrainerBase):
         wrote them; cached packed weights are stale."""
         self.group.refresh_plans(); self.aux_group.refresh_plans()
         self._drop_inference_graphs()
+
+    def checkpoint_modules(self) -> Dict[str, torch.nn.Module]:
+        """{name: module} of what a checkpoint holds beside the training state: no discriminator here."""
+        return {"comp_model": self.model}
 
     # ---------------------------------------------------------------- one step
     def forward_losses(self, ctx: Ctx, real: Tensor, vq_indices: Optional[Tensor], beta_rate: Tensor, beta_vq: Tensor,
@@ -137,12 +129,8 @@ class DualBetaCondRateDistortionVqCodeTrainer(BetaPairTrainerBase):
         w_rate = self.rate_loss.sample_weights(N, H * W, rate_w.expand(N).contiguous(), device=self.device)
         out = nets.analysis_forward(ctx, m, x, beta_rate, beta_vq, vq_indices=vq_indices, noise_y=noise_y, noise_z=noise_z, generator=self.noise_gen,
                                     weights=w_rate, scale=1.0)
-        feat_1, feats = nets.decoder_get_feats(ctx, m.decoder, out["quantized_code"]["y"], beta_rate, beta_vq)
-        pred_embed, logits = nets.estimator_forward(ctx, m.vq_estimator, feat_1)
-        pq = m.vq_model.post_quant_conv
-        out_idx, lat = ops.argmax_lut(logits.data, m.vq_model.quantize.embedding.weight, pq.weight.reshape(pq.out_channels, -1).contiguous(), pq.bias)
-        fake = nets.fusion_decode(ctx, m.fusion_module, m.vq_model.decoder, A.const(lat), feats, w=1.0)
-        gt_lat, gt_idx = out["gt_vq_latent"], out["gt_vq_indices"]
+        s = nets.synthesis_forward(ctx, m, out["quantized_code"]["y"], beta_rate, beta_vq)
+        fake, gt_lat, gt_idx = s["fake"], out["gt_vq_latent"], out["gt_vq_indices"]
         L = {"rate": out["loss"]}
         if self.distortion_type == "MSSSIMLoss":           # raises, naming the size, when min(H, W) <= 160
             L["distortion"] = A.ms_ssim_loss(ctx, fake, x, self.w["distortion"])
@@ -150,53 +138,36 @@ class DualBetaCondRateDistortionVqCodeTrainer(BetaPairTrainerBase):
             L["distortion"] = A.l1_loss(ctx, fake, x, self.w["distortion"])
         else:
             L["distortion"] = A.mse_loss(ctx, fake, x, self.w["distortion"] * self.distortion_factor)
-        if self.lpips is not None:
-            from .lpips import lpips_loss
-            L["perceptual"] = lpips_loss(ctx, self.lpips, x, fake, self.w["perceptual"])
-        else:
-            L["perceptual"] = torch.zeros(1, device=self.device)
+        L["perceptual"] = self.perceptual_term(ctx, x, fake)
         w_cd = sample_loss_weights(self.w["code_distortion"], self.code_distortion_reduction, N, gt_lat[0].numel(), vq_w, device=self.device)
-        L["code_distortion"] = A.mse_loss_weighted(ctx, pred_embed, gt_lat, w_cd)
+        L["code_distortion"] = A.mse_loss_weighted(ctx, s["pred_embed"], gt_lat, w_cd)
         w_ce = sample_loss_weights(self.w["code_ce"], self.code_ce_reduction, N, gt_idx[0].numel(), vq_w, device=self.device)
-        L["code_ce"] = A.focal_cross_entropy_loss_weighted(ctx, logits, gt_idx, w_ce, self.code_ce_gamma)
-        out.update(real=x, fake=fake, pred_embed=pred_embed, logits=logits, out_vq_indices=out_idx,
-                   qbpp=float((out["q_bits_y"].double().sum() + out["q_bits_z"].double().sum()).item()) / (N * H * W))
+        L["code_ce"] = A.focal_cross_entropy_loss_weighted(ctx, s["logits"], gt_idx, w_ce, self.code_ce_gamma)
+        out.update(s, real=x, qbpp=self.qbpp(out["q_bits_y"], out["q_bits_z"], x))
         return L, out
 
     def optimize_aux_parameters(self) -> float:
         """rate_distortion_vq_code_trainer.py `optimize_aux_parameters`: EntropyBottleneck.loss() on the parameters as they are NOW
         (after the main step), its gradient w.r.t. `quantiles`, averaged over the ranks, one Adam step."""
         self.aux_group.zero_grad()
-        aux = A.eb_aux_loss(Ctx([self.aux_group]), self.model.entropy_model_z)
-        allreduce_mean_(self.aux_group.grad, self.dist)
-        self.aux_opt.step()
+        aux = A.eb_aux_loss(Ctx([self.aux_group]), self.model.entropy_model_z)     # writes the gradient itself: no tape to run, no clip
+        self.apply_gradients(None, self.aux_opt)
         return float(aux.item())
 
     def optimize_parameters(self, current_iter: int, data_dict: Dict) -> Optional[Dict[str, float]]:
         real = data_dict["real_images"]
-        n = real.shape[0]
-        beta_rate, beta_vq = data_dict.get("beta_rate"), data_dict.get("beta_vq")
-        if beta_rate is None or beta_vq is None:
-            beta_rate, beta_vq = self.sample_beta_pair(n if self.sample_beta_batch else 1)
-        self.last_beta_rate, self.last_beta_vq = beta_rate, beta_vq
+        beta_rate, beta_vq = self.step_beta_pair(data_dict, real.shape[0])
         self.group.zero_grad()
         ctx = Ctx([self.group])
         L, o = self.forward_losses(ctx, real, data_dict.get("vq_indices"), beta_rate, beta_vq, data_dict.get("noise_y"), data_dict.get("noise_z"))
         log = {k: float(v.item()) for k, v in L.items()}
         total = sum(log.values())
-        if loss_anomaly(total, self.dist, self.device):  # base_trainer.py:235-245: skip the step -- on EVERY rank or on none
-            ctx.tape = []
+        if self.skip_step(total, ctx):
             return None
-        ctx.backward()
-        allreduce_mean_(self.group.grad, self.dist)
-        gscale = None
-        if self.clip:                                   # clip_grad_norm_ over comp_model.parameters(): `quantiles` has no gradient yet
-            gscale = K.clip_scale(K.reduce_loss(K.SUM_SQ, self.group.grad, None, 1.0), self.clip)
         lr_now = self.sched.lr()
-        self.opt.step(lr_now, gscale)
+        self.apply_gradients(ctx, self.opt, lr_now, self.clip)     # clip_grad_norm_ over comp_model.parameters(): `quantiles` has no gradient yet
         self.sched.step()
         aux = self.optimize_aux_parameters()
         self._drop_inference_graphs()
-        vq_acc = float((o["out_vq_indices"] == o["gt_vq_indices"]).float().mean().item())
-        log.update(total=total, qbpp=o["qbpp"], vq_acc=vq_acc, lr=lr_now, aux=aux)
+        log.update(total=total, qbpp=o["qbpp"], vq_acc=self.vq_acc(o), lr=lr_now, aux=aux)
         return log

@@ -28,7 +28,6 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .. import ops
 from ..layers import invalidate_weight_caches
 from ..registry import LOSS_REGISTRY, TRAINER_REGISTRY
 from . import autograd as A
@@ -119,10 +118,25 @@ class Adam:
         g.refresh_plans()
 
 
+def adam_state(opt: Adam) -> Dict:
+    """The Adam part of a training state: the group's moments (host copies), the step count and the group's size."""
+    g = opt.group
+    return {"m": g.m.detach().cpu().clone(), "v": g.v.detach().cpu().clone(), "t": int(opt.t), "numel": int(g.numel())}
+
+
+def load_adam_state(opt: Adam, s_: Dict, tag: str) -> None:
+    """adam_state's entries of the group saved as `tag` back into `opt`; ValueError when the group's size is another."""
+    g = opt.group
+    if int(s_["numel"]) != g.numel():
+        raise ValueError(f"training state: {tag} group has {s_['numel']} parameters, this model {g.numel()}")
+    g.m.copy_(s_["m"].to(g.m.device)); g.v.copy_(s_["v"].to(g.v.device))
+    opt.t = int(s_["t"])
+
+
 class BetaPairTrainerBase:
     """What the GAN-stage trainers and the rate-distortion trainer (rd_trainer.py) share: the perceptual network and its weights, the
-    beta-pair samplers (drawing from `self.rng`), validation, and the forgetting of captured inference graphs.  Expects `self.model`,
-    `self.rng` and `self.device`."""
+    beta-pair samplers (drawing from `self.rng`), the pieces of a step (beta pair, anomaly skip, perceptual term, a group's gradient step, the
+    logged vq_acc / qbpp), validation, the forgetting of captured graphs.  Expects `self.model`, `rng`, `device`, `dist`, `w`, `sample_beta_batch`."""
 
     def _build_lpips(self, weight: float, lpips_state: Optional[Dict[str, Tensor]], dev) -> None:
         self.lpips = None
@@ -189,6 +203,47 @@ class BetaPairTrainerBase:
         beta_vq = sample_beta_grid(self.rng, m.max_beta_vq, m.num_beta_levels, n)
         return beta_rate, beta_vq
 
+    # ---------------------------------------------------------------- the pieces of optimize_parameters
+    def step_beta_pair(self, data_dict: Dict, n: int):
+        """The pair this step trains with: the data dict's, else drawn per image (sample_beta_batch) or once; kept as last_beta_*."""
+        beta_rate, beta_vq = data_dict.get("beta_rate"), data_dict.get("beta_vq")
+        if beta_rate is None or beta_vq is None:
+            beta_rate, beta_vq = self.sample_beta_pair(n if self.sample_beta_batch else 1)
+        self.last_beta_rate, self.last_beta_vq = beta_rate, beta_vq
+        return beta_rate, beta_vq
+
+    def perceptual_term(self, ctx: Ctx, real: Tensor, fake) -> Tensor:
+        """LPIPS(real, fake) x w['perceptual'] on the tape, or a zero when the term is off."""
+        if self.lpips is None:
+            return torch.zeros(1, device=self.device)
+        from .lpips import lpips_loss
+        return lpips_loss(ctx, self.lpips, real, fake, self.w["perceptual"])
+
+    def skip_step(self, total: float, ctx: Ctx) -> bool:
+        """base_trainer.py:235-245: a total loss that is non-finite or > 1e4 skips the step -- on EVERY rank or on none -- and drops its pass."""
+        if not loss_anomaly(total, self.dist, self.device):
+            return False
+        ctx.discard()
+        return True
+
+    def apply_gradients(self, ctx: Optional[Ctx], opt: Adam, lr: Optional[float] = None, clip: Optional[float] = None) -> None:
+        """A group's step: backward (`ctx` None: the gradient is written already), mean over the ranks, clip_grad_norm_'s scale, Adam at `lr`."""
+        if ctx is not None:
+            ctx.backward()
+        grad = opt.group.grad
+        allreduce_mean_(grad, self.dist)
+        gscale = K.clip_scale(K.reduce_loss(K.SUM_SQ, grad, None, 1.0), clip) if clip else None
+        opt.step(lr, gscale)
+
+    @staticmethod
+    def qbpp(bits_y: Tensor, bits_z: Tensor, x: Tensor) -> float:
+        """Bits per pixel of the quantised likelihoods over the batch x (the logged `qbpp`, calc_g_loss :199)."""
+        return float((bits_y.double().sum() + bits_z.double().sum()).item()) / (x.shape[0] * x.shape[2] * x.shape[3])
+
+    @staticmethod
+    def vq_acc(o: Dict) -> float:
+        return float((o["out_vq_indices"] == o["gt_vq_indices"]).float().mean().item())
+
 
 @TRAINER_REGISTRY.register()
 class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
@@ -237,20 +292,16 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
     # ---------------------------------------------------------------- training state (base_trainer.py:178-214 saves optimizer + scheduler state)
     def training_state(self, current_iter: int) -> Dict:
         st = {"iter": int(current_iter), "rng": self.rng.get_state()}
-        for tag, grp, opt_, sch in (("g", self.g_group, self.g_opt, self.g_sched), ("d", self.d_group, self.d_opt, self.d_sched)):
-            st[tag] = {"m": grp.m.detach().cpu().clone(), "v": grp.v.detach().cpu().clone(), "t": int(opt_.t), "last_epoch": int(sch.last_epoch),
-                       "numel": int(grp.numel())}
+        for tag, opt_, sch in (("g", self.g_opt, self.g_sched), ("d", self.d_opt, self.d_sched)):
+            st[tag] = dict(adam_state(opt_), last_epoch=int(sch.last_epoch))
         if self.gumbel_gen is not None:
             st["gumbel_gen"] = self.gumbel_gen.get_state().clone()
         return st
 
     def load_training_state(self, st: Dict) -> int:
-        for tag, grp, opt_, sch in (("g", self.g_group, self.g_opt, self.g_sched), ("d", self.d_group, self.d_opt, self.d_sched)):
-            s_ = st[tag]
-            if int(s_["numel"]) != grp.numel():
-                raise ValueError(f"training state: {tag} group has {s_['numel']} parameters, this model {grp.numel()}")
-            grp.m.copy_(s_["m"].to(grp.m.device)); grp.v.copy_(s_["v"].to(grp.v.device))
-            opt_.t, sch.last_epoch = int(s_["t"]), int(s_["last_epoch"])
+        for tag, opt_, sch in (("g", self.g_opt, self.g_sched), ("d", self.d_opt, self.d_sched)):
+            load_adam_state(opt_, st[tag], tag)
+            sch.last_epoch = int(st[tag]["last_epoch"])
         if "rng" in st:
             self.rng.set_state(st["rng"])
         if self.gumbel_gen is not None:
@@ -265,6 +316,10 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
         self.g_group.refresh_plans(); self.d_group.refresh_plans()
         self._drop_inference_graphs()
 
+    def checkpoint_modules(self) -> Dict[str, torch.nn.Module]:
+        """{name: module} of what a checkpoint holds beside the training state: <name>_iterXXXXXXX.pth.tar = {'iter', name: state_dict}."""
+        return {"comp_model": self.model, "discriminator": self.D}
+
     @torch.no_grad()
     def generator_forward(self, ctx: Ctx, real: Tensor, vq_indices: Optional[Tensor], beta_rate, beta_vq):
         """run_comp_model (:116-133) -> forward (hyperprior_dc_vic_model.py:208-274, is_train, fix_entropy_models)."""
@@ -274,21 +329,13 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
         y = m.comp_encode(x, gt_lat, gt_idx, enc_kwargs=dict(beta_1=beta_rate, beta_2=beta_vq), feat=feat)
         e = m._entropy_encode_side(y, want_symbols=False)                                      # fix_entropy_models: no grad
         y_hat = e["y_hat"]
-        feat_1, feats = nets.decoder_get_feats(ctx, m.decoder, y_hat, beta_rate, beta_vq)
-        pred_embed, logits = nets.estimator_forward(ctx, m.vq_estimator, feat_1)
-        pq = m.vq_model.post_quant_conv
-        out_idx, lat = ops.argmax_lut(logits.data, m.vq_model.quantize.embedding.weight, pq.weight.reshape(pq.out_channels, -1).contiguous(), pq.bias)
-        z = A.const(lat)
+        gumbel = None
         if self.gumbel_sampling:
-            # :254-260: the decoder reads the sample; out_vq_indices stays the argmax (vq_acc)
-            noise = self.draw_gumbel_noise(logits.data)
-            _, z = A.gumbel_vq_latent(ctx, logits, noise, m.vq_model.quantize.embedding.weight, pq.weight.reshape(pq.out_channels, -1).contiguous(),
-                                      pq.bias, self.gumbel_tau)
-        fake = nets.fusion_decode(ctx, m.fusion_module, m.vq_model.decoder, z, feats, w=1.0)
-        N, _, H, W = x.shape
-        qbpp = float((e["bits_y"].double().sum() + e["bits_z"].double().sum()).item()) / (N * H * W)
-        return dict(real=x, fake=fake, pred_embed=pred_embed, logits=logits, gt_vq_latent=gt_lat, gt_vq_indices=gt_idx, out_vq_indices=out_idx,
-                    y_hat=y_hat, qbpp=qbpp)
+            # :254-260, one e per logit: [N, n_embed] over the VQ token grid
+            n_embed = m.vq_model.quantize.embedding.weight.shape[0]
+            gumbel = (self.draw_gumbel_noise(x.new_empty((x.shape[0], n_embed) + tuple(gt_lat.shape[-2:]))), self.gumbel_tau)
+        s = nets.synthesis_forward(ctx, m, y_hat, beta_rate, beta_vq, gumbel)
+        return dict(s, real=x, gt_vq_latent=gt_lat, gt_vq_indices=gt_idx, y_hat=y_hat, qbpp=self.qbpp(e["bits_y"], e["bits_z"], x))
 
     def draw_gumbel_noise(self, logits: Tensor) -> Tensor:
         """e ~ Exp(1) of the logits' shape from the trainer's generator: -log(e) is the Gumbel noise F.gumbel_softmax draws."""
@@ -299,11 +346,7 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
         w = self.w
         log = {}
         log["distortion"] = A.mse_loss(ctx, o["fake"], o["real"], w["distortion"] * self.distortion_factor)   # 0.25: MSELoss on [0,1], ((a+1)/2-(b+1)/2)^2
-        if self.lpips is not None:
-            from .lpips import lpips_loss
-            log["perceptual"] = lpips_loss(ctx, self.lpips, o["real"], o["fake"], w["perceptual"])
-        else:
-            log["perceptual"] = torch.zeros(1, device=self.device)
+        log["perceptual"] = self.perceptual_term(ctx, o["real"], o["fake"])
         g_fake = nets.discriminator_forward(ctx, self.D, o["fake"], beta_rate, beta_vq)
         log["adv"] = self.calc_adv_loss(ctx, g_fake, o["gt_vq_indices"])
         w_cd = w["code_distortion"] * (o["gt_vq_latent"].numel() if self.code_distortion_reduction == "sum" else 1)
@@ -320,27 +363,16 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
 
     def optimize_parameters(self, current_iter: int, data_dict: Dict) -> Optional[Dict[str, float]]:
         real = data_dict["real_images"]
-        vq_indices = data_dict.get("vq_indices")
-        n = real.shape[0]
-        beta_rate, beta_vq = data_dict.get("beta_rate"), data_dict.get("beta_vq")
-        if beta_rate is None or beta_vq is None:
-            beta_rate, beta_vq = self.sample_beta_pair(n if self.sample_beta_batch else 1)
-        self.last_beta_rate, self.last_beta_vq = beta_rate, beta_vq
+        beta_rate, beta_vq = self.step_beta_pair(data_dict, real.shape[0])
         # ---------------------------------------------------------------- train G
         self.g_group.zero_grad()
         ctx = Ctx([self.g_group])                      # D's parameters receive no gradient here (requires_grad_(False), :146)
-        o = self.generator_forward(ctx, real, vq_indices, beta_rate, beta_vq)
+        o = self.generator_forward(ctx, real, data_dict.get("vq_indices"), beta_rate, beta_vq)
         g_log = self.calc_g_loss(ctx, o, beta_rate, beta_vq)
         total = sum(float(v.item()) for v in g_log.values())
-        if loss_anomaly(total, self.dist, self.device):  # base_trainer.py:235-245: skip the step -- on EVERY rank or on none
-            ctx.tape = []
+        if self.skip_step(total, ctx):
             return None
-        ctx.backward()
-        allreduce_mean_(self.g_group.grad, self.dist)
-        gscale = None
-        if self.clip:
-            gscale = K.clip_scale(K.reduce_loss(K.SUM_SQ, self.g_group.grad, None, 1.0), self.clip)
-        self.g_opt.step(self.g_sched.lr(), gscale)
+        self.apply_gradients(ctx, self.g_opt, self.g_sched.lr(), self.clip)
         self._drop_inference_graphs()
         lr_now = self.g_sched.lr()
         self.g_sched.step()
@@ -351,14 +383,11 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
         self.last_fake = fake_det
         d_real, d_fake = self.run_discriminator(dctx, o["real"], fake_det, beta_rate, beta_vq)
         l_real, l_fake = self.calc_d_loss(dctx, d_real, d_fake, o["gt_vq_indices"])
-        dctx.backward()
-        allreduce_mean_(self.d_group.grad, self.dist)
-        self.d_opt.step(self.d_sched.lr())
+        self.apply_gradients(dctx, self.d_opt, self.d_sched.lr())
         self.d_sched.step()
-        vq_acc = float((o["out_vq_indices"] == o["gt_vq_indices"]).float().mean().item())
         log = {k: float(v.item()) for k, v in g_log.items()}
         out_d_real, out_d_fake = self.calc_avg_d_score_for_log(d_real, d_fake)
-        log.update(total=total, qbpp=o["qbpp"], vq_acc=vq_acc, lr=lr_now, d_real=float(l_real.item()), d_fake=float(l_fake.item()),
+        log.update(total=total, qbpp=o["qbpp"], vq_acc=self.vq_acc(o), lr=lr_now, d_real=float(l_real.item()), d_fake=float(l_fake.item()),
                    d_total=float(l_real.item()) + float(l_fake.item()), out_d_real=out_d_real, out_d_fake=out_d_fake)
         return log
 

@@ -30,7 +30,7 @@ dict of lpips.LPIPS(net='alex'), loaded with weights_only=True); its weights can
 perceptual weight is an ERROR unless --allow_synthetic_lpips opts into synthetic AlexNet weights (benchmarks / plumbing only).
 `model.gumbel_sampling: true` (GAN trainers only; the rate-distortion trainer refuses it): the decoder reads a hard Gumbel-softmax
 sample of the code logits instead of their argmax (csrc/gumbel.hip), so the distortion, perceptual and adversarial losses reach the VQ
-estimator; `model.gumbel_kwargs` may set `tau` (> 0, default 1) and nothing else (read_gumbel_options); the noise comes from a device
+estimator; `model.gumbel_kwargs` may set `tau` (> 0, default 1) and nothing else (train/build.py read_gumbel_options); the noise comes from a device
 generator the trainer owns, saved in and restored from the training state (rank 0's); rank 0 prints `[train] VQ sampling: ...`.
 --save_step also writes training_state_iter*.pth.tar (Adam moments, step counts, scheduler epochs, beta-sampler RNG; the
 reference saves optimizer + scheduler state too, base_trainer.py:178-214) and --resume continues from it.
@@ -40,18 +40,18 @@ Validation (base_trainer.py:130-192): every --eval_step iterations (YAML `eval_s
 <save_dir>/eval_result.csv (--resume carries the earlier rows over).  Its time is left out of samples/s.
 GAN loss: `DualBetaCondGanDistortionVqCodeTrainer` (PatchGAN, VanillaGANLoss) or `DualBetaCondOasisGanDistortionVqFusionTrainer`
 (config/dc_vic_oasis.yaml: 257-way per-token discriminator, OasisGANLoss), chosen by --gan {vanilla,oasis}, else the YAML's
-`trainer.type`, else `loss.gan_loss.type`, else the discriminator's `out_nc` (1 -> vanilla, n_embed + 1 -> oasis); see choose_gan_trainer.
+`trainer.type`, else `loss.gan_loss.type`, else the discriminator's `out_nc` (1 -> vanilla, n_embed + 1 -> oasis); see choose_gan_trainer
+in dc_vic_amd/train/build.py, which holds the choice of the trainer, the mapping of the YAML's sections to its arguments and build_trainer.
 Rate-distortion (config/exp1_stage1_2.yaml): `trainer.type: DualBetaCondRateDistortionVqCodeTrainer` builds dc_vic_amd/train/rd_trainer.py
 (choose_trainer, in front of choose_gan_trainer): the whole model but the VQGAN trains on rate + distortion + perceptual + code losses with
 per-sample weights exp(beta) or beta + offset (`trainer.beta_policy`, `beta_offset`, `sample_beta_batch`; `loss.rate_loss` and the
 `reduction: none` entries are read), `optim.aux_optimizer.lr` drives the entropy bottleneck's quantiles.  No discriminator is built and
-no discriminator_* file is written or read; --gan with such a config is an error, and so is the stage 1-1 `RateDistortionVqCodeTrainer`
+no discriminator_* file is written or read (the trainer's checkpoint_modules names the files of a checkpoint); --gan with such a config is an error, and so is the stage 1-1 `RateDistortionVqCodeTrainer`
 (an unconditioned model that is not built).  A stage 1-2 run starts from a dual-conditioned checkpoint (--model_path) or synthetic weights.
 """
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 import time
@@ -63,135 +63,13 @@ import torch
 sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dc_vic_amd import BaseConfig, build_comp_model  # noqa: E402
 from dc_vic_amd.parallel import launched_by_a_launcher, pin_rank_cpus, self_launch  # noqa: E402
-from dc_vic_amd.registry import TRAINER_REGISTRY  # noqa: E402
-from dc_vic_amd.train import DualBetaCondTamingNLayerDiscriminator  # noqa: E402  (registers both stage-3 trainers)
+from dc_vic_amd.train import DualBetaCondTamingNLayerDiscriminator  # noqa: E402
+from dc_vic_amd.train.build import (DEFAULT_DISCRIMINATOR, build_rd_trainer, build_trainer, choose_gan_trainer, choose_trainer, get_in,  # noqa: E402,F401
+                                    read_gumbel_options)
 from dc_vic_amd.train.data import HostFeed, TrainFeed, list_train_images, read_train_dataset  # noqa: E402
-from dc_vic_amd.train.losses import build_code_ce_loss, read_loss_section  # noqa: E402
+from dc_vic_amd.train.losses import read_loss_section  # noqa: E402
+from dc_vic_amd.train.trainer import DEFAULT_LOSS  # noqa: E402
 from dc_vic_amd.train.validation import EvalCSV, eval_image_paths, load_eval_images  # noqa: E402
-
-
-def _get(d, *keys, default=None):
-    for k in keys:
-        try:
-            d = d[k]
-        except (KeyError, TypeError):
-            return default
-    return d
-
-
-VANILLA_TRAINER, OASIS_TRAINER = "DualBetaCondGanDistortionVqCodeTrainer", "DualBetaCondOasisGanDistortionVqFusionTrainer"
-_TRAINER_KIND = {VANILLA_TRAINER: "vanilla", OASIS_TRAINER: "oasis"}
-_LOSS_KIND = {"VanillaGANLoss": "vanilla", "OasisGANLoss": "oasis"}
-
-
-def choose_gan_trainer(opt, gan_flag=None):
-    """(kind, trainer class name, reason) for a parsed config (pure: no GPU, no model).  Order: the --gan flag; `trainer.type`;
-    `loss.gan_loss.type`; the discriminator's `out_nc` (absent or 1 -> vanilla, n_embed + 1 -> oasis).  SystemExit for an unknown
-    type, for `trainer.mc_sampling` (not built) and for a choice the discriminator cannot serve: OASIS needs out_nc = n_embed + 1
-    of the VQ codebook and keep_shape (one 257-way classification per token), the BCE PatchGAN must not get that discriminator."""
-    n_embed = _get(opt, "subnet", "vq_model", "n_embed")
-    out_nc = int(_get(opt, "discriminator", "out_nc", default=1))
-    keep_shape = bool(_get(opt, "discriminator", "keep_shape", default=False))
-    if _get(opt, "trainer", "mc_sampling", default=False):
-        raise SystemExit("trainer.mc_sampling: true is not built (the reference's split of a batch into a generator half and a discriminator "
-                         "half with dataset-supplied VQ indices): set it to false")
-    t_type, l_type = _get(opt, "trainer", "type"), _get(opt, "loss", "gan_loss", "type")
-    if gan_flag is not None:
-        if gan_flag not in ("vanilla", "oasis"):
-            raise SystemExit(f"--gan {gan_flag}: unknown, expected vanilla or oasis")
-        kind, reason = gan_flag, f"--gan {gan_flag}"
-    elif t_type is not None:
-        if t_type not in _TRAINER_KIND:
-            raise SystemExit(f"trainer.type: {t_type} is unknown, expected {VANILLA_TRAINER} or {OASIS_TRAINER}")
-        kind, reason = _TRAINER_KIND[t_type], f"trainer.type: {t_type}"
-    elif l_type is not None:
-        if l_type not in _LOSS_KIND:
-            raise SystemExit(f"loss.gan_loss.type: {l_type} is unknown, expected VanillaGANLoss or OasisGANLoss")
-        kind, reason = _LOSS_KIND[l_type], f"loss.gan_loss.type: {l_type}"
-    elif out_nc == 1:
-        kind, reason = "vanilla", "discriminator.out_nc: 1"
-    elif n_embed is not None and out_nc == int(n_embed) + 1:
-        kind, reason = "oasis", f"discriminator.out_nc: {out_nc} = n_embed + 1"
-    else:
-        raise SystemExit(f"discriminator.out_nc: {out_nc} names no GAN loss (1 -> vanilla, n_embed + 1 = "
-                         f"{'?' if n_embed is None else int(n_embed) + 1} -> oasis) and neither --gan, trainer.type nor loss.gan_loss.type is given")
-    if gan_flag is None and t_type in _TRAINER_KIND and l_type in _LOSS_KIND and _TRAINER_KIND[t_type] != _LOSS_KIND[l_type]:
-        raise SystemExit(f"trainer.type: {t_type} cannot train with loss.gan_loss.type: {l_type}")
-    if kind == "oasis":
-        if n_embed is None:
-            raise SystemExit(f"OASIS GAN loss ({reason}) needs subnet.vq_model.n_embed to size the discriminator's classes")
-        if out_nc != int(n_embed) + 1:
-            raise SystemExit(f"OASIS GAN loss ({reason}) cannot train a discriminator with out_nc: {out_nc}; it needs n_embed + 1 = {int(n_embed) + 1}")
-        if not keep_shape:
-            raise SystemExit(f"OASIS GAN loss ({reason}) cannot train a discriminator with keep_shape: false; its logits must lie on the VQ token grid")
-    elif n_embed is not None and out_nc == int(n_embed) + 1 and out_nc != 1:
-        raise SystemExit(f"vanilla GAN loss ({reason}) cannot train a discriminator with out_nc: {out_nc} (n_embed + 1 classes: an OASIS "
-                         "discriminator); use --gan oasis or out_nc: 1")
-    return kind, (OASIS_TRAINER if kind == "oasis" else VANILLA_TRAINER), reason
-
-
-def read_gumbel_options(opt):
-    """(gumbel_sampling, tau) of a parsed config's `model` section for the GAN-stage trainers (pure: no GPU, no model), called after
-    choose_gan_trainer.  `model.gumbel_kwargs` may hold `tau` (a number > 0, default 1) and nothing else: the sample is the reference's
-    F.gumbel_softmax(logits, dim=1, hard=True, **gumbel_kwargs), so `hard` and `dim` would raise there and `eps` does nothing.
-    SystemExit names the key and its value.  The keywords are checked with the option off too, as the model's constructor takes them."""
-    from dc_vic_amd.train.trainer import gumbel_tau
-    kw = _get(opt, "model", "gumbel_kwargs", default=None)
-    try:
-        tau = gumbel_tau(dict(kw) if kw else None)
-    except ValueError as e:
-        raise SystemExit(str(e))
-    return bool(_get(opt, "model", "gumbel_sampling", default=False)), tau
-
-
-RD_TRAINER, RD_STAGE_1_1 = "DualBetaCondRateDistortionVqCodeTrainer", "RateDistortionVqCodeTrainer"
-
-
-def choose_trainer(opt, gan_flag=None):
-    """(kind, trainer class name, reason) for a parsed config (pure: no GPU, no model): kind "rd" for the stage 1-2 rate-distortion
-    trainer (`trainer.type: DualBetaCondRateDistortionVqCodeTrainer`), else choose_gan_trainer's answer.  SystemExit for the stage 1-1
-    trainer (not built), for --gan together with a rate-distortion trainer type, and for what that trainer does not build."""
-    t_type = _get(opt, "trainer", "type")
-    if t_type == RD_STAGE_1_1:
-        raise SystemExit(f"trainer.type: {t_type} (stage 1-1, config/exp1_stage1_1.yaml) is not built: it trains the unconditioned model, which needs "
-                         "HyperpriorCharmVicModel, ElicVqCatScEncoder, ElicFeatFusionDecoder and LinearWarmupScheduler; the dual-conditioned "
-                         f"stage 1-2 trainer {RD_TRAINER} is")
-    if t_type != RD_TRAINER:
-        return choose_gan_trainer(opt, gan_flag)
-    if gan_flag is not None:
-        raise SystemExit(f"--gan {gan_flag} cannot go with trainer.type: {t_type}: the rate-distortion trainer has no discriminator and no GAN loss")
-    if _get(opt, "model", "gumbel_sampling", default=False):
-        raise SystemExit("model.gumbel_sampling: true is not built (the Gumbel-softmax sampling of the VQ indices in training mode): set it to false")
-    policy = _get(opt, "trainer", "beta_policy", default="linear")
-    if policy not in ("linear", "exp"):
-        raise SystemExit(f"trainer.beta_policy: {policy} is unknown, expected linear or exp")
-    if _get(opt, "loss", "gan_loss") is not None:
-        raise SystemExit(f"loss.gan_loss has no place under trainer.type: {t_type}: it trains no GAN loss")
-    return "rd", RD_TRAINER, f"trainer.type: {t_type}"
-
-
-def build_rd_trainer(opt, losses, model, dist, seed, lpips_state):
-    """The rate-distortion trainer from the YAML's `trainer`, `optim` and `loss` sections -> (trainer, the `[train]` log line)."""
-    from dc_vic_amd.train.rd_trainer import DEFAULT_RD_LOSS
-    lw = {k: v for k, v in losses["weights"].items() if k in DEFAULT_RD_LOSS}
-    rate = losses["rate"] or dict(loss_weight=None, reduction="mean")
-    if rate["loss_weight"] is not None:
-        lw["rate"] = rate["loss_weight"]
-    kw = dict(beta_policy=_get(opt, "trainer", "beta_policy", default="linear"), beta_offset=float(_get(opt, "trainer", "beta_offset", default=1.0)),
-              sample_beta_batch=bool(_get(opt, "trainer", "sample_beta_batch", default=False)), rate_reduction=rate["reduction"],
-              code_ce_gamma=losses["code_ce"]["gamma"], code_ce_reduction=losses["code_ce"]["reduction"],
-              code_distortion_reduction=losses["code_distortion_reduction"])
-    trainer = TRAINER_REGISTRY.get(RD_TRAINER)(
-        model, lr=float(_get(opt, "optim", "g_optimizer", "lr", default=1e-4)), aux_lr=float(_get(opt, "optim", "aux_optimizer", "lr", default=1e-3)),
-        milestones=list(_get(opt, "optim", "g_scheduler", "milestones", default=[300000])), gamma=float(_get(opt, "optim", "g_scheduler", "gamma", default=0.1)),
-        clip_max_norm=_get(opt, "optim", "clip_max_norm", default=1.0), loss_weights=lw, dist=dist, seed=seed, lpips_state=lpips_state,
-        distortion_factor=losses["distortion_factor"], distortion_type=losses["distortion_type"],
-        gumbel_sampling=bool(_get(opt, "model", "gumbel_sampling", default=False)), **kw)
-    line = (f"rate-distortion trainer: {RD_TRAINER}; beta_policy {kw['beta_policy']}" + (f" (offset {kw['beta_offset']:g})" if kw["beta_policy"] == "linear" else "")
-            + f", sample_beta_batch {kw['sample_beta_batch']}; weights " + ", ".join(f"{k} {trainer.w[k]:g}" for k in DEFAULT_RD_LOSS)
-            + f"; reductions rate {kw['rate_reduction']}, code_distortion {kw['code_distortion_reduction']}, code_ce {kw['code_ce_reduction']}"
-            + f" (gamma {kw['code_ce_gamma']:g}); distortion {trainer.distortion_type}")
-    return trainer, line
 
 
 class CropDataset:
@@ -312,9 +190,10 @@ def main():
     if (a.data_workers is not None and a.data_workers < 0) or a.data_depth < 1:
         raise SystemExit(f"--data_workers {a.data_workers} / --data_depth {a.data_depth}: need workers >= 0 and depth >= 1")
     opt0 = BaseConfig.fromfile(a.config_path, {"is_train": True})
-    gan_kind, trainer_name, gan_reason = choose_trainer(opt0, a.gan)       # before any GPU work
+    gan_kind = choose_trainer(opt0, a.gan)[0]                              # before any GPU work
     losses = read_loss_section(opt0)                                       # likewise: every `loss` entry is honoured or refused
-    gumbel_on, gumbel_tau_ = read_gumbel_options(opt0) if gan_kind != "rd" else (False, 1.0)    # likewise
+    if gan_kind != "rd":
+        read_gumbel_options(opt0)                                          # likewise
     listing = list_training_set(a, opt0)                                   # likewise: the `dataset` section, the folder, its listing
     if a.eval_dataset_root is not None:
         try:                                          # a folder named on the command line must hold PNGs: checked before any GPU work
@@ -353,16 +232,11 @@ def main():
         load_synth_weights(model, 1234)
     else:
         model.load_learned_weight(ckpt_path=a.model_path)
-    is_rd = gan_kind == "rd"                          # no discriminator, no discriminator_* file
-    dopt = dict(_get(opt, "discriminator", default=None) or dict(type="DualBetaCondTamingNLayerDiscriminator", input_nc=11, n_layers=3, ndf=64,
-                                                                  norm_type="none", max_beta_1=3.0, max_beta_2=3.5, L=10, cond_ch=8,
-                                                                  use_pi=False, include_x=True))
+    dopt = dict(get_in(opt, "discriminator", default=None) or DEFAULT_DISCRIMINATOR)
     dopt.pop("type", None)
     torch.manual_seed(a.seed)                       # identical D initialisation on every rank
-    D = None if is_rd else DualBetaCondTamingNLayerDiscriminator(**dopt).to(device)
-    lw = dict(losses["weights"])
-    from dc_vic_amd.train.trainer import DEFAULT_LOSS
-    w_perc = lw.get("perceptual", DEFAULT_LOSS["perceptual"])
+    D = None if gan_kind == "rd" else DualBetaCondTamingNLayerDiscriminator(**dopt).to(device)     # the rate-distortion trainer has none
+    w_perc = losses["weights"].get("perceptual", DEFAULT_LOSS["perceptual"])
     lpips_state = None
     if a.lpips_path:
         lpips_state = torch.load(a.lpips_path, map_location="cpu", weights_only=True)
@@ -373,41 +247,23 @@ def main():
             raise SystemExit(msg + "  Pass --lpips_path STATE_DICT, set loss.perceptual_loss.loss_weight: 0, or opt in with --allow_synthetic_lpips.")
         if rank == 0:
             print("[train] WARNING: " + msg, file=sys.stderr, flush=True)
-    if is_rd:
-        trainer, rd_line = build_rd_trainer(opt, losses, model, dist, a.seed * 100 + rank, lpips_state)
-        if rank == 0:
-            print("[train] " + rd_line, flush=True)
-            print("[train] losses: " + losses["line"], flush=True)
-    else:
-        if rank == 0:
-            w_src = "loss.gan_loss.loss_weight" if "gan" in lw else "default, no reference YAML pins it" if gan_kind == "oasis" else "default"
-            print(f"[train] GAN trainer: {gan_kind} ({trainer_name}), chosen by {gan_reason}; generator-side gan weight "
-                  f"{lw.get('gan', DEFAULT_LOSS['gan']):g} ({w_src})", flush=True)
-            print("[train] losses: " + losses["line"] + "; weights " + ", ".join(f"{k} {lw.get(k, v):g}" for k, v in DEFAULT_LOSS.items()), flush=True)
-            print("[train] VQ sampling: " + (f"gumbel-softmax (tau {gumbel_tau_:g})" if gumbel_on else "argmax"), flush=True)
-        trainer = TRAINER_REGISTRY.get(trainer_name)(
-            model, D, lr_g=float(_get(opt, "optim", "g_optimizer", "lr", default=1e-4)), lr_d=float(_get(opt, "optim", "d_optimizer", "lr", default=1e-4)),
-            milestones=list(_get(opt, "optim", "g_scheduler", "milestones", default=[300000])), gamma=float(_get(opt, "optim", "g_scheduler", "gamma", default=0.1)),
-            clip_max_norm=_get(opt, "optim", "clip_max_norm", default=1.0), loss_weights=lw,
-            sample_beta_batch=bool(_get(opt, "trainer", "sample_beta_batch", default=True)), dist=dist, seed=a.seed * 100 + rank,
-            d_milestones=_get(opt, "optim", "d_scheduler", "milestones", default=None), d_gamma=_get(opt, "optim", "d_scheduler", "gamma", default=None),
-            lpips_state=lpips_state, code_ce_loss=build_code_ce_loss(losses["code_ce"], lw.get("code_ce", DEFAULT_LOSS["code_ce"])),
-            distortion_factor=losses["distortion_factor"], code_distortion_reduction=losses["code_distortion_reduction"],
-            gumbel_sampling=gumbel_on, gumbel_kwargs=dict(tau=gumbel_tau_))
+    trainer, lines = build_trainer(opt, losses, model, D, dist, a.seed * 100 + rank, lpips_state, a.gan)
+    if rank == 0:
+        for line in lines:
+            print("[train] " + line, flush=True)
     start_iter = 0
     if a.resume:
         # base_trainer.py:178-214: comp_model / discriminator / training_state files of one iteration
         st = torch.load(a.resume, map_location="cpu", weights_only=False)        # our own file (numpy RNG state inside)
         d_ = os.path.dirname(a.resume)
         it_tag = os.path.basename(a.resume).replace("training_state_", "")
-        model.load_state_dict(torch.load(os.path.join(d_, "comp_model_" + it_tag), map_location="cpu", weights_only=True)["comp_model"])
-        if not is_rd:
-            D.load_state_dict(torch.load(os.path.join(d_, "discriminator_" + it_tag), map_location="cpu", weights_only=True)["discriminator"])
+        for name, mod in trainer.checkpoint_modules().items():
+            mod.load_state_dict(torch.load(os.path.join(d_, f"{name}_" + it_tag), map_location="cpu", weights_only=True)[name])
         trainer.resync_parameters()
         start_iter = trainer.load_training_state(st)
-    total_iter = a.total_iter or int(_get(opt, "total_iter", default=500000))
-    eval_step = a.eval_step if a.eval_step is not None else int(_get(opt, "eval_step", default=10000))
-    eval_root = a.eval_dataset_root or _get(opt, "dataset", "eval_dataset", "root_dir", default=None)
+    total_iter = a.total_iter or int(get_in(opt, "total_iter", default=500000))
+    eval_step = a.eval_step if a.eval_step is not None else int(get_in(opt, "eval_step", default=10000))
+    eval_root = a.eval_dataset_root or get_in(opt, "dataset", "eval_dataset", "root_dir", default=None)
     if a.eval_dataset_root is None and eval_root and eval_step > 0 and rank == 0:
         if os.path.isdir(eval_root) and glob(os.path.join(eval_root, "*.png")):
             eval_images = load_eval_images(eval_root)
@@ -460,11 +316,9 @@ def main():
                     dist.barrier()
                 t_eval += time.perf_counter() - tv
             if a.save_dir and a.save_step and it % a.save_step == 0 and rank == 0:
-                torch.save({"iter": it, "comp_model": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}},
-                           os.path.join(a.save_dir, f"comp_model_iter{it:07d}.pth.tar"))
-                if not is_rd:
-                    torch.save({"iter": it, "discriminator": {k: v.detach().cpu().clone() for k, v in D.state_dict().items()}},
-                               os.path.join(a.save_dir, f"discriminator_iter{it:07d}.pth.tar"))
+                for name, mod in trainer.checkpoint_modules().items():
+                    torch.save({"iter": it, name: {k: v.detach().cpu().clone() for k, v in mod.state_dict().items()}},
+                               os.path.join(a.save_dir, f"{name}_iter{it:07d}.pth.tar"))
                 torch.save(trainer.training_state(it), os.path.join(a.save_dir, f"training_state_iter{it:07d}.pth.tar"))
     finally:
         if data is not None:

@@ -75,17 +75,11 @@ def build_model():
 
 
 def build_trainer(m, lr=1e-4, seed=3, **kw):
-    """The trainer as scripts/train.py builds it from the YAML's sections."""
+    """The trainer as scripts/train.py builds it from the YAML's sections (train/build.py), under the test's lr, seed and overrides."""
     from dc_vic_amd.train import DualBetaCondRateDistortionVqCodeTrainer
+    from dc_vic_amd.train.build import rd_trainer_kwargs
     from dc_vic_amd.train.losses import read_loss_section
-    opt = section()
-    r = read_loss_section(opt)
-    lw = dict(r["weights"], rate=r["rate"]["loss_weight"])
-    lw.pop("gan", None)
-    args = dict(lr=lr, aux_lr=1e-3, clip_max_norm=1.0, loss_weights=lw, beta_policy=opt["trainer"]["beta_policy"],
-                sample_beta_batch=opt["trainer"]["sample_beta_batch"], seed=seed, rate_reduction=r["rate"]["reduction"],
-                code_ce_gamma=r["code_ce"]["gamma"], code_ce_reduction=r["code_ce"]["reduction"],
-                code_distortion_reduction=r["code_distortion_reduction"], distortion_factor=r["distortion_factor"])
+    args = dict(rd_trainer_kwargs(section(), read_loss_section(section())), lr=lr, seed=seed)
     args.update(kw)
     return DualBetaCondRateDistortionVqCodeTrainer(m, **args)
 

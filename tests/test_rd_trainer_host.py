@@ -79,6 +79,59 @@ def test_cli_refusals_before_any_gpu_work(cli, sections, change, flag, words):
         cli.choose_trainer(sections["exp1_stage1_1.yaml"])
 
 
+# the four fall-back values of a config without an `optim` section (the golden sections hold `loss` and `trainer` only)
+OPTIM_DEFAULTS = dict(milestones=[300000], gamma=0.1, clip_max_norm=1.0)      # and lr 1e-4, under each trainer's own name
+
+
+def test_rd_trainer_kwargs_of_the_stage_1_2_section(cli, sections):
+    """train/build.py's mapping against the arguments scripts/train.py's build_rd_trainer, tools/train_bench.py's rd_trainer and
+    tests/test_gpu_rd_trainer.py's build_trainer each spelt before it existed (the three agreed, defaults filled in), written out."""
+    from dc_vic_amd.train.build import build_rd_trainer, rd_trainer_kwargs
+    from dc_vic_amd.train.losses import read_loss_section
+    opt = sections["exp1_stage1_2.yaml"]
+    assert rd_trainer_kwargs(opt, read_loss_section(opt)) == dict(
+        lr=1e-4, aux_lr=1e-3, **OPTIM_DEFAULTS,
+        loss_weights=dict(distortion=50.0, perceptual=1.0, code_distortion=0.006, code_ce=0.003, rate=0.5),
+        beta_policy="exp", beta_offset=1.0, sample_beta_batch=True, rate_reduction="none", code_ce_gamma=2.0, code_ce_reduction="none",
+        code_distortion_reduction="none", distortion_factor=0.25, distortion_type="MSELoss", gumbel_sampling=False)
+    # an `optim` section is read, not defaulted over
+    o2 = dict(opt, optim=dict(g_optimizer=dict(lr=2e-4), aux_optimizer=dict(lr=5e-3), g_scheduler=dict(milestones=[10, 20], gamma=0.5), clip_max_norm=None))
+    kw = rd_trainer_kwargs(o2, read_loss_section(o2))
+    assert (kw["lr"], kw["aux_lr"], kw["milestones"], kw["gamma"], kw["clip_max_norm"]) == (2e-4, 5e-3, [10, 20], 0.5, None)
+    assert cli.build_rd_trainer is build_rd_trainer          # the CLI's names are the package's, not wrappers
+
+
+@pytest.mark.parametrize("cfg", ["exp1_stage3.yaml", "exp1_stage1_3.yaml", "dc_vic_oasis.yaml", "dc_vic_patchgan.yaml", "focal"])
+def test_gan_trainer_kwargs_of_the_gan_sections(cli, sections, cfg):
+    """The arguments scripts/train.py's main() passed to the GAN trainers, written out: the two stage configs give every weight and a
+    CrossEntropyLoss object, the two discriminator configs (no `loss` section) leave the trainer's defaults; "focal" is stage 1-3 with
+    the FocalCrossEntropyLoss entry the reference's stage 1-1 file carries, mean -> sum."""
+    from dc_vic_amd.train.build import gan_trainer_kwargs, read_gumbel_options
+    from dc_vic_amd.train.losses import CrossEntropyLoss, FocalCrossEntropyLoss, read_loss_section
+    opt = sections["exp1_stage1_3.yaml" if cfg == "focal" else cfg]
+    if cfg == "focal":
+        opt = dict(opt, loss=dict(opt["loss"], code_ce_loss=dict(type="FocalCrossEntropyLoss", loss_weight=0.05, gamma=2.0, reduction="sum")),
+                   model=dict(gumbel_sampling=True, gumbel_kwargs=dict(tau=0.5)))
+    assert cli.read_gumbel_options is read_gumbel_options
+    kw = gan_trainer_kwargs(opt, read_loss_section(opt), read_gumbel_options(opt))
+    ce = kw.pop("code_ce_loss")
+    has_loss = opt.get("loss") is not None
+    lw = dict(distortion=50.0, perceptual=1.0, gan=0.01, code_distortion=1.0, code_ce=0.05 if cfg == "focal" else 0.5) if has_loss else {}
+    assert kw == dict(lr_g=1e-4, lr_d=1e-4, **OPTIM_DEFAULTS, loss_weights=lw, sample_beta_batch=True, d_milestones=None, d_gamma=None,
+                      distortion_factor=0.25, code_distortion_reduction="mean", gumbel_sampling=cfg == "focal",
+                      gumbel_kwargs=dict(tau=0.5 if cfg == "focal" else 1.0))
+    if cfg == "focal":
+        assert type(ce) is FocalCrossEntropyLoss and (ce.loss_weight, ce.gamma, ce.reduction) == (0.05, 2.0, "sum")
+    elif has_loss:
+        assert type(ce) is CrossEntropyLoss and ce.loss_weight == 0.5
+    else:
+        assert ce is None
+    # the discriminator's schedule is its own YAML entry
+    o2 = dict(opt, optim=dict(d_optimizer=dict(lr=3e-4), d_scheduler=dict(milestones=[7], gamma=0.3)))
+    kw = gan_trainer_kwargs(o2, read_loss_section(o2), read_gumbel_options(o2))
+    assert (kw["lr_g"], kw["lr_d"], kw["d_milestones"], kw["d_gamma"], kw["milestones"]) == (1e-4, 3e-4, [7], 0.3, [300000])
+
+
 def test_main_parameter_rule_and_beta_weights():
     from dc_vic_amd.train.rd_trainer import DEFAULT_RD_LOSS, LOG_KEYS, beta_loss_weights, is_main_parameter
     assert is_main_parameter("encoder.conv1.weight") and is_main_parameter("entropy_model_z._matrix0") and is_main_parameter("fusion_module.x.weight")

@@ -67,18 +67,13 @@ def main():
 
 def rd_trainer(m, dist, rank, distortion="MSELoss"):
     from dc_vic_amd.train import DualBetaCondRateDistortionVqCodeTrainer
+    from dc_vic_amd.train.build import rd_trainer_kwargs
     from dc_vic_amd.train.losses import read_loss_section
     with open(os.path.join(ROOT, "tests", "golden", "reference_loss_sections.json")) as f:
         opt = json.load(f)["exp1_stage1_2.yaml"]
     if distortion != "MSELoss":
         opt["loss"]["distortion_loss"] = dict(type=distortion, loss_weight=opt["loss"]["distortion_loss"]["loss_weight"])
-    r = read_loss_section(opt)
-    lw = {k: v for k, v in r["weights"].items() if k != "gan"}
-    lw["rate"] = r["rate"]["loss_weight"]
-    return DualBetaCondRateDistortionVqCodeTrainer(
-        m, loss_weights=lw, beta_policy=opt["trainer"]["beta_policy"], sample_beta_batch=opt["trainer"]["sample_beta_batch"], dist=dist, seed=rank,
-        rate_reduction=r["rate"]["reduction"], code_ce_gamma=r["code_ce"]["gamma"], code_ce_reduction=r["code_ce"]["reduction"],
-        code_distortion_reduction=r["code_distortion_reduction"], distortion_factor=r["distortion_factor"], distortion_type=r["distortion_type"])
+    return DualBetaCondRateDistortionVqCodeTrainer(m, dist=dist, seed=rank, **rd_trainer_kwargs(opt, read_loss_section(opt)))
 
 
 def gan_trainer(a, m, dev, dist, rank):

@@ -254,6 +254,57 @@ class LayerNormC(nn.Module):
         return ops.layernorm_c(x, self.weight, self.bias, self.eps)
 
 
+class BatchNorm2d(nn.Module):
+    """torch.nn.BatchNorm2d(num_features, eps, momentum) stand-in with torch's state-dict entries (weight, bias, running_mean,
+    running_var, int64 num_batches_tracked).  It has a training forward only, on the tape (train/autograd.batch_norm, csrc/bn_train.hip):
+    the normalised GAN discriminators never run in eval mode."""
+
+    def __init__(self, num_features: int, eps: float = 1e-5, momentum: float = 0.1):
+        super().__init__()
+        self.num_features, self.eps, self.momentum = int(num_features), float(eps), float(momentum)
+        self.weight = nn.Parameter(torch.ones(num_features), requires_grad=False)
+        self.bias = nn.Parameter(torch.zeros(num_features), requires_grad=False)
+        self.register_buffer("running_mean", torch.zeros(num_features))
+        self.register_buffer("running_var", torch.ones(num_features))
+        self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+
+    def forward(self, x):
+        raise RuntimeError("BatchNorm2d runs on the training tape only (train/autograd.batch_norm)")
+
+
+class ActNorm(nn.Module):
+    """taming's ActNorm(num_features) stand-in (taming/modules/util.py:10-69, logdet not built): loc and scale [1, C, 1, 1] and the
+    uint8 buffer `initialized`.  The first training call sets loc = -mean and scale = 1 / (std_unbiased + 1e-6) from its batch
+    (train/autograd.act_norm).  The flag lives on the device for the state dict; the host reads it once, and again after a
+    load_state_dict, never per step."""
+
+    def __init__(self, num_features: int):
+        super().__init__()
+        self.num_features = int(num_features)
+        self.loc = nn.Parameter(torch.zeros(1, num_features, 1, 1), requires_grad=False)
+        self.scale = nn.Parameter(torch.ones(1, num_features, 1, 1), requires_grad=False)
+        self.register_buffer("initialized", torch.tensor(0, dtype=torch.uint8))
+        self._initialized_host: Optional[bool] = None
+        self.flag_reads = 0          # device reads of the flag so far (tests)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self._initialized_host = None
+
+    def is_initialized(self) -> bool:
+        if self._initialized_host is None:
+            self._initialized_host = bool(self.initialized.item())
+            self.flag_reads += 1
+        return self._initialized_host
+
+    def mark_initialized(self) -> None:
+        self.initialized.fill_(1)
+        self._initialized_host = True
+
+    def forward(self, x):
+        raise RuntimeError("ActNorm runs on the training tape only (train/autograd.act_norm)")
+
+
 class Act(nn.Module):
     """Placeholder that keeps nn.Sequential indices aligned with the reference (activations are fused)."""
 

@@ -193,3 +193,24 @@ def synth_discriminator_state(shapes: Dict[str, Iterable], seed: int = 5) -> Dic
         shp = tuple(int(v) for v in shapes[name])
         out[name] = torch.randn(shp, generator=g) * (0.05 if len(shp) > 1 else 0.02)
     return out
+
+
+def synth_norm_discriminator_state(shapes: Dict[str, Iterable], seed: int = 5) -> Dict[str, torch.Tensor]:
+    """synth_discriminator_state for a discriminator with BatchNorm or ActNorm layers: the same draws in the same order, then what a
+    norm layer's state must be -- `running_var` positive (0.5 + 25 |draw|), `running_mean` of some size (5 x draw), a BatchNorm
+    `weight` near one (1 + 5 x draw), `num_batches_tracked` the int64 3 and ActNorm's `initialized` the uint8 0, so that the first
+    training call initialises it."""
+    out = synth_discriminator_state(shapes, seed)
+    for name in sorted(shapes):
+        stem, _, leaf = name.rpartition(".")
+        if leaf == "running_var":
+            out[name] = 0.5 + 25.0 * out[name].abs()
+        elif leaf == "running_mean":
+            out[name] = 5.0 * out[name]
+        elif leaf == "weight" and stem + ".running_var" in shapes:
+            out[name] = 1.0 + 5.0 * out[name]
+        elif leaf == "num_batches_tracked":
+            out[name] = torch.tensor(3, dtype=torch.long)
+        elif leaf == "initialized":
+            out[name] = torch.tensor(0, dtype=torch.uint8)
+    return out

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..layers import Conv2d, ConvTranspose2d, GroupNorm, LayerNormC, Linear, copy_kernel_flags, invalidate_weight_caches
+from ..layers import ActNorm, BatchNorm2d, Conv2d, ConvTranspose2d, GroupNorm, LayerNormC, Linear, copy_kernel_flags, invalidate_weight_caches
 from . import kernels as K
 
 Tensor = torch.Tensor
@@ -369,6 +369,45 @@ def layer_norm_c(ctx: Ctx, x: Var, mod: LayerNormC) -> Var:
             K.ew(K.EW_ADD, None, gw, tmp[:Cc], out=gw)
             K.ew(K.EW_ADD, None, gb, tmp[Cc:], out=gb)
     return ctx.op(ops.layernorm_c(xd, mod.weight, mod.bias, mod.eps), backward)
+
+
+_NORM_ACTS = (ops.ACT_NONE, ops.ACT_LRELU02)
+
+
+def batch_norm(ctx: Ctx, x: Var, mod: BatchNorm2d, act: int = ops.ACT_NONE) -> Var:
+    """nn.BatchNorm2d in training mode (+ fused LeakyReLU(0.2)): this call's own batch statistics, the running statistics and
+    num_batches_tracked updated now, the gradients of csrc/bn_train.hip (dgamma / dbeta added into the flat gradient buffer)."""
+    if act not in _NORM_ACTS:
+        raise ValueError("batch_norm: only LeakyReLU(0.2) may be fused")
+    if not mod.training:
+        raise NotImplementedError("batch_norm: the eval-mode forward (running statistics) is not built: the discriminators stay in train mode")
+    xd = x.data
+    y, mean, rstd = K.bn_train_fwd(xd, mod.weight, mod.bias, mod.running_mean, mod.running_var, mod.momentum, mod.eps, act)
+    mod.num_batches_tracked.add_(1)
+
+    def backward(g):
+        acc(x, K.bn_train_bwd(xd, g, y if act != ops.ACT_NONE else None, mean, rstd, mod.weight, ctx.pgrad(mod.weight), ctx.pgrad(mod.bias),
+                              accumulate=True, act=act))
+    return ctx.op(y, backward)
+
+
+def act_norm(ctx: Ctx, x: Var, mod: ActNorm, act: int = ops.ACT_NONE) -> Var:
+    """taming's ActNorm (+ fused LeakyReLU(0.2)): scale * (x + loc), initialised from the first training batch (loc = -mean,
+    scale = 1 / (unbiased std + 1e-6)); dloc / dscale are added into the flat gradient buffer."""
+    if act not in _NORM_ACTS:
+        raise ValueError("act_norm: only LeakyReLU(0.2) may be fused")
+    xd = x.data
+    if mod.training and not mod.is_initialized():
+        mean, std = K.bn_stats(xd)
+        mod.loc.data.copy_(mean.neg_().view_as(mod.loc))                # once per module: C values
+        mod.scale.data.copy_(std.add_(1e-6).reciprocal_().view_as(mod.scale))
+        mod.mark_initialized()
+    y = K.actnorm_fwd(xd, mod.loc, mod.scale, act)
+
+    def backward(g):
+        acc(x, K.actnorm_bwd(xd, g, y if act != ops.ACT_NONE else None, mod.loc, mod.scale, ctx.pgrad(mod.loc), ctx.pgrad(mod.scale),
+                             accumulate=True, act=act))
+    return ctx.op(y, backward)
 
 
 # ------------------------------------------------------------------------------------------- elementwise

@@ -29,6 +29,47 @@ DEFAULT_DISCRIMINATOR = dict(type="DualBetaCondTamingNLayerDiscriminator", input
                              max_beta_2=3.5, L=10, cond_ch=8, use_pi=False, include_x=True)
 
 
+PATCHGAN, UNET = "DualBetaCondTamingNLayerDiscriminator", "OasisDualBetaCondTamingNLayerDiscriminator"
+VQ_TOKEN_STRIDE = 8         # pixels per VQ token: the OASIS loss classifies one logit column per token
+
+
+def read_discriminator(opt) -> Dict[str, Any]:
+    """The `discriminator` section of a parsed config (pure: no GPU, no module) -> dict(type, kwargs: the section's other keys unchanged,
+    norm_type and norm_kwargs as they take effect, norm_type_given, line: the `[train]` log line).  A config without the section gets
+    DEFAULT_DISCRIMINATOR.  SystemExit, naming the key and its value, for an unknown type and for everything the classes do not build."""
+    from . import nets
+    d = dict(get_in(opt, "discriminator", default=None) or DEFAULT_DISCRIMINATOR)
+    d_type = d.pop("type", PATCHGAN)
+    if d_type not in (PATCHGAN, UNET):
+        raise SystemExit(f"discriminator.type: {d_type} is unknown, expected {PATCHGAN} or {UNET}")
+    given = "norm_type" in d or bool(d.get("use_actnorm", False))
+    try:
+        norm_type, nk = nets.resolve_norm(d.get("norm_type", "none"), bool(d.get("use_actnorm", False)), d.get("norm_kwargs"))
+        nets.refuse_y_hat_cond(d.get("y_hat_cond", False))
+        n_layers = int(d.get("n_layers", 3))
+        if n_layers < 1:
+            raise ValueError(f"n_layers: {n_layers}, needs at least 1")
+        if d_type == UNET:
+            nets.check_unet_options(n_layers, int(d.get("num_upsample", 1)), int(d.get("cond_ch", 8)), int(d.get("input_nc", 3)))
+    except (NotImplementedError, ValueError) as e:
+        raise SystemExit(f"discriminator.{e}")
+    line = f"discriminator: {d_type}, n_layers {n_layers}, norm {norm_type}"
+    if norm_type == "batchnorm":
+        line += f" (eps {nk.get('eps', 1e-5):g}, momentum {nk.get('momentum', 0.1):g})"
+    if d_type == UNET:
+        line += f", num_upsample {int(d.get('num_upsample', 1))}"
+    if not given:
+        line += "; the YAML names no norm_type: the reference's class default is batchnorm, none is in effect here"
+    return dict(type=d_type, kwargs=d, norm_type=norm_type, norm_kwargs=nk, norm_type_given=given, line=line)
+
+
+def build_discriminator(opt, device):
+    """(the discriminator `opt` asks for, on `device`; its `[train]` log line).  The caller seeds torch's generator first."""
+    from ..registry import DISCRIMINATOR_REGISTRY
+    r = read_discriminator(opt)
+    return DISCRIMINATOR_REGISTRY.get(r["type"])(**r["kwargs"]).to(device), r["line"]
+
+
 def choose_gan_trainer(opt, gan_flag=None):
     """(kind, trainer class name, reason) for a parsed config (pure: no GPU, no model).  Order: the --gan flag; `trainer.type`;
     `loss.gan_loss.type`; the discriminator's `out_nc` (absent or 1 -> vanilla, n_embed + 1 -> oasis).  SystemExit for an unknown
@@ -67,7 +108,13 @@ def choose_gan_trainer(opt, gan_flag=None):
             raise SystemExit(f"OASIS GAN loss ({reason}) needs subnet.vq_model.n_embed to size the discriminator's classes")
         if out_nc != int(n_embed) + 1:
             raise SystemExit(f"OASIS GAN loss ({reason}) cannot train a discriminator with out_nc: {out_nc}; it needs n_embed + 1 = {int(n_embed) + 1}")
-        if not keep_shape:
+        if get_in(opt, "discriminator", "type") == UNET:          # keep_shape does not apply: the up blocks set the logits' grid
+            n_layers, n_up = int(get_in(opt, "discriminator", "n_layers", default=3)), int(get_in(opt, "discriminator", "num_upsample", default=1))
+            if 2 ** (n_layers - n_up) != VQ_TOKEN_STRIDE:
+                raise SystemExit(f"OASIS GAN loss ({reason}) cannot train a U-Net discriminator with n_layers: {n_layers} and num_upsample: {n_up}; "
+                                 f"its logits lie on a grid of 2^(n_layers - num_upsample) = {2 ** max(n_layers - n_up, 0)} pixels, the VQ tokens on one of "
+                                 f"{VQ_TOKEN_STRIDE}")
+        elif not keep_shape:
             raise SystemExit(f"OASIS GAN loss ({reason}) cannot train a discriminator with keep_shape: false; its logits must lie on the VQ token grid")
     elif n_embed is not None and out_nc == int(n_embed) + 1 and out_nc != 1:
         raise SystemExit(f"vanilla GAN loss ({reason}) cannot train a discriminator with out_nc: {out_nc} (n_embed + 1 classes: an OASIS "

@@ -1,5 +1,5 @@
 """ctypes wrappers of the training-step kernels (csrc/train.hip, include/dcvic.h "Training step"; csrc/chan_ce.hip; csrc/sample_loss.hip,
-include/dcvic_sample_loss.h; csrc/rate_train.hip, include/dcvic_rate.h; csrc/gumbel.hip, include/dcvic_gumbel.h; csrc/msssim_loss.hip, include/dcvic_msssim_loss.h; csrc/data.hip, include/dcvic_data.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
+include/dcvic_sample_loss.h; csrc/rate_train.hip, include/dcvic_rate.h; csrc/gumbel.hip, include/dcvic_gumbel.h; csrc/msssim_loss.hip, include/dcvic_msssim_loss.h; csrc/data.hip, include/dcvic_data.h; csrc/bn_train.hip, include/dcvic_bn.h).  torch only supplies device memory; every computation is a HIP kernel launch on the current stream."""
 from __future__ import annotations
 
 import ctypes
@@ -224,6 +224,78 @@ def sq_err_sample(a: Tensor, b: Tensor, w: Tensor, want_grad: bool = True, want_
     check(lib().dcvic_sq_err_sample_f32(_p(a), a.stride(0) if N > 1 else M, _p(b), _p(_flat_f32(w, N, "sq_err_sample: sample weights")), _p(loss),
                                         _p(da), _p(per), _p(ws), N, M, _stream()), "sq_err_sample")
     return loss, da, per
+
+
+# ------------------------------------------------------------------------------------------- batch statistics (csrc/bn_train.hip)
+def _bn_views(name: str, x: Tensor, *others: Optional[Tensor]):
+    """(N, C, HW, workspace, its bytes) of [N, C, H, W] views of one shape, each with its own batch stride."""
+    shape = _chk4(x, f"{name} x")
+    for t in others:
+        if t is not None and _chk4(t, name) != shape:
+            raise ValueError(f"{name}: a tensor of {tuple(t.shape)} against x {tuple(x.shape)}")
+    N, Cc, H, W = shape
+    need = int(lib().dcvic_bn_workspace_bytes(N, Cc, H * W))
+    ws = _workspace((need + 7) // 8, x.device, "bn", torch.float64)
+    return N, Cc, H * W, ws, ws.numel() * 8
+
+
+def bn_stats(x: Tensor):
+    """(mean [C], unbiased standard deviation [C]) of x [N, C, H, W] over (N, H, W)  (dcvic_bn_stats_f32)."""
+    N, Cc, HW, ws, wsb = _bn_views("bn_stats", x)
+    mean, std = torch.empty(Cc, dtype=torch.float32, device=x.device), torch.empty(Cc, dtype=torch.float32, device=x.device)
+    check(lib().dcvic_bn_stats_f32(_p(x), _bs(x), _p(mean), _p(std), _p(ws), wsb, N, Cc, HW, _stream()), "bn_stats")
+    return mean, std
+
+
+def bn_train_fwd(x: Tensor, gamma: Tensor, beta: Tensor, running_mean: Optional[Tensor], running_var: Optional[Tensor], momentum: float,
+                 eps: float, act: int = ops.ACT_NONE, out: Optional[Tensor] = None):
+    """BatchNorm2d in training mode with an optional fused LeakyReLU(0.2) (dcvic_bn_train_fwd_f32): (y, save_mean [C], save_rstd [C]);
+    the running statistics, when given, are updated in place."""
+    y = out if out is not None else torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    N, Cc, HW, ws, wsb = _bn_views("bn_train_fwd", x, y)
+    for t, what in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _flat_f32(t, Cc, f"bn_train_fwd: {what}")
+    mean, rstd = torch.empty(Cc, dtype=torch.float32, device=x.device), torch.empty(Cc, dtype=torch.float32, device=x.device)
+    check(lib().dcvic_bn_train_fwd_f32(_p(x), _bs(x), _p(y), _bs(y), _p(gamma), _p(beta), _p(running_mean), _p(running_var), float(momentum),
+                                       float(eps), _p(mean), _p(rstd), int(act), _p(ws), wsb, N, Cc, HW, _stream()), "bn_train_fwd")
+    return y, mean, rstd
+
+
+def bn_train_bwd(x: Tensor, g: Tensor, y: Optional[Tensor], save_mean: Tensor, save_rstd: Tensor, gamma: Tensor, dgamma: Optional[Tensor] = None,
+                 dbeta: Optional[Tensor] = None, accumulate: bool = True, act: int = ops.ACT_NONE, dx: Optional[Tensor] = None) -> Tensor:
+    """dx of bn_train_fwd for the gradient g on its output y (read only with an act); dgamma / dbeta [C], when given, are added to
+    (accumulate) or overwritten  (dcvic_bn_train_bwd_f32)."""
+    dx = dx if dx is not None else torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    N, Cc, HW, ws, wsb = _bn_views("bn_train_bwd", x, g, y, dx)
+    for t, what in ((save_mean, "save_mean"), (save_rstd, "save_rstd"), (gamma, "gamma"), (dgamma, "dgamma"), (dbeta, "dbeta")):
+        _flat_f32(t, Cc, f"bn_train_bwd: {what}")
+    check(lib().dcvic_bn_train_bwd_f32(_p(x), _bs(x), _p(g), _bs(g), _p(y), _bs(y), _p(save_mean), _p(save_rstd), _p(gamma), _p(dx), _bs(dx),
+                                       _p(dgamma), _p(dbeta), 1 if accumulate else 0, int(act), _p(ws), wsb, N, Cc, HW, _stream()), "bn_train_bwd")
+    return dx
+
+
+def actnorm_fwd(x: Tensor, loc: Tensor, scale: Tensor, act: int = ops.ACT_NONE, out: Optional[Tensor] = None) -> Tensor:
+    """act(scale[c] * (x + loc[c]))  (dcvic_actnorm_fwd_f32); loc / scale hold C values ([1, C, 1, 1] is welcome)."""
+    y = out if out is not None else torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    N, Cc, H, W = _chk4(x, "actnorm_fwd x")
+    if _chk4(y, "actnorm_fwd y") != (N, Cc, H, W):
+        raise ValueError(f"actnorm_fwd: y {tuple(y.shape)} against x {tuple(x.shape)}")
+    _flat_f32(loc, Cc, "actnorm_fwd: loc"), _flat_f32(scale, Cc, "actnorm_fwd: scale")
+    check(lib().dcvic_actnorm_fwd_f32(_p(x), _bs(x), _p(y), _bs(y), _p(loc), _p(scale), int(act), N, Cc, H * W, _stream()), "actnorm_fwd")
+    return y
+
+
+def actnorm_bwd(x: Tensor, g: Tensor, y: Optional[Tensor], loc: Tensor, scale: Tensor, dloc: Optional[Tensor] = None, dscale: Optional[Tensor] = None,
+                accumulate: bool = True, act: int = ops.ACT_NONE, dx: Optional[Tensor] = None) -> Tensor:
+    """dx = scale * g' of actnorm_fwd; dloc = scale * sum g' and dscale = sum g' (x + loc), when given, are added to (accumulate) or
+    overwritten  (dcvic_actnorm_bwd_f32)."""
+    dx = dx if dx is not None else torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    N, Cc, HW, ws, wsb = _bn_views("actnorm_bwd", x, g, y, dx)
+    for t, what in ((loc, "loc"), (scale, "scale"), (dloc, "dloc"), (dscale, "dscale")):
+        _flat_f32(t, Cc, f"actnorm_bwd: {what}")
+    check(lib().dcvic_actnorm_bwd_f32(_p(x), _bs(x), _p(g), _bs(g), _p(y), _bs(y), _p(loc), _p(scale), _p(dx), _bs(dx), _p(dloc), _p(dscale),
+                                      1 if accumulate else 0, int(act), _p(ws), wsb, N, Cc, HW, _stream()), "actnorm_bwd")
+    return dx
 
 
 # ------------------------------------------------------------------------------------------- image distortions (csrc/msssim_loss.hip)

@@ -21,7 +21,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..elic import BetaScaleShiftModule, ChengNLAM, ConvTranspose2d, FourierEncoding, ResidualBottleneckBlocks
-from ..layers import Act, Conv2d, Linear
+from ..layers import Act, ActNorm, BatchNorm2d, Conv2d, Linear
+from ..registry import DISCRIMINATOR_REGISTRY
 from . import autograd as A
 from .autograd import Ctx, Var
 
@@ -334,50 +335,199 @@ def synthesis_forward(ctx: Ctx, model, y_hat, beta_rate, beta_vq, gumbel: Option
 
 
 # ------------------------------------------------------------------------------------------- discriminator
+@DISCRIMINATOR_REGISTRY.register()
 class DualBetaCondTamingNLayerDiscriminator(nn.Module):
-    """PatchGAN conditioned on (beta_rate, beta_vq): state-dict keys `main.{0,2,5,8,11}.{weight,bias}`, `mlp.{0,2}.{weight,bias}`
-    as in the reference (norm_type 'none' -> Identity layers keep their Sequential indices, biases on)."""
+    """PatchGAN conditioned on (beta_rate, beta_vq): state-dict keys `main.{0,2,5,8,11}.{weight,bias}` (n_layers 3),
+    `mlp.{0,2}.{weight,bias}` as in the reference.  norm_type 'none' -> Identity layers keep their Sequential indices, biases on;
+    'batchnorm' -> `main.{3,6,9}.{weight,bias,running_mean,running_var,num_batches_tracked}` and no bias on the convolutions in front
+    of them; 'actnorm' (or use_actnorm) -> `main.{3,6,9}.{loc,scale,initialized}`.  The Python default stays 'none' (the
+    reference's class default is 'batchnorm'; every shipped YAML names its norm_type)."""
 
     def __init__(self, input_nc: int = 11, ndf: int = 64, out_nc: int = 1, n_layers: int = 3, keep_shape: bool = False,
                  use_actnorm: bool = False, norm_type: str = "none", norm_kwargs: dict = {}, max_beta_1: float = -1.0,
                  max_beta_2: float = -1.0, L: int = 10, cond_ch: int = 8, use_pi: bool = False, include_x: bool = True,
                  y_hat_cond: bool = False, y_hat_in_ch=None, y_hat_out_ch=None, weight_init: bool = True, **kwargs):
         super().__init__()
-        if norm_type != "none" or use_actnorm or y_hat_cond or n_layers != 3:
-            raise NotImplementedError("only the shipped PatchGAN (n_layers 3, norm_type none, no y_hat condition) is built")
+        self.norm_type, self.norm_kwargs = resolve_norm(norm_type, use_actnorm, norm_kwargs)
+        refuse_y_hat_cond(y_hat_cond)
+        if int(n_layers) < 1:
+            raise ValueError(f"n_layers: {n_layers!r}, needs at least 1")
         kw = 4
+        use_bias = self.norm_type != "batchnorm"        # the reference: no conv bias in front of a BatchNorm's own shift
         seq = [Conv2d(input_nc, ndf, kw, 2, 1), Act()]
         mult = 1
         for n in range(1, n_layers):
             prev, mult = mult, min(2 ** n, 8)
-            seq += [Conv2d(ndf * prev, ndf * mult, kw, 2, 1), nn.Identity(), Act()]
+            seq += [Conv2d(ndf * prev, ndf * mult, kw, 2, 1, bias=use_bias), make_norm(ndf * mult, self.norm_type, self.norm_kwargs), Act()]
         kl = 3 if keep_shape else kw
         prev, mult = mult, min(2 ** n_layers, 8)
-        seq += [Conv2d(ndf * prev, ndf * mult, kl, 1, 1), nn.Identity(), Act()]
+        seq += [Conv2d(ndf * prev, ndf * mult, kl, 1, 1, bias=use_bias), make_norm(ndf * mult, self.norm_type, self.norm_kwargs), Act()]
         seq += [Conv2d(ndf * mult, out_nc, kl, 1, 1)]
         self.main = nn.Sequential(*seq)
+        self.n_layers = int(n_layers)
         self.embed_1 = FourierEncoding(L=L, max_beta=max_beta_1, use_pi=use_pi, include_x=include_x)
         self.embed_2 = FourierEncoding(L=L, max_beta=max_beta_2, use_pi=use_pi, include_x=include_x)
         mlp_in = 2 * (2 * L + 1) if include_x else 2 * 2 * L
         self.mlp = nn.Sequential(Linear(mlp_in, cond_ch), Act(), Linear(cond_ch, cond_ch))
         self.cond_ch = cond_ch
         self.y_hat_cond = False
-        if weight_init:         # taming weights_init: conv weights ~ N(0, 0.02)
-            for m in self.main:
-                if isinstance(m, Conv2d):
-                    nn.init.normal_(m.weight, 0.0, 0.02)
+        if weight_init:
+            weights_init(self.main)
 
 
-def discriminator_forward(ctx: Ctx, D: DualBetaCondTamingNLayerDiscriminator, x: Var, beta_1, beta_2) -> Var:
+NORM_TYPES = ("none", "batchnorm", "actnorm")
+_NORMS_NOT_BUILT = ("instancenorm", "groupnorm", "layernorm")
+
+
+def resolve_norm(norm_type: str, use_actnorm: bool = False, norm_kwargs: Optional[dict] = None) -> Tuple[str, Dict[str, float]]:
+    """(norm type, BatchNorm2d's keywords) of a discriminator's options, as get_norm_layer reads them
+    (taming_nlayer_discriminator.py:11-26,53-59): `use_actnorm: true` means actnorm; `norm_kwargs` may hold `eps` and `momentum` as
+    numbers for batchnorm and nothing else.  Every other norm type, key or value is refused with the setting and its value."""
+    if use_actnorm:
+        norm_type = "actnorm"
+    if norm_type in _NORMS_NOT_BUILT:
+        raise NotImplementedError(f"norm_type: {norm_type} is not built (none, batchnorm and actnorm are)")
+    if norm_type not in NORM_TYPES:
+        raise NotImplementedError(f"norm_type: {norm_type!r} is unknown, expected one of {', '.join(NORM_TYPES)}")
+    out = {}
+    for k, v in dict(norm_kwargs or {}).items():
+        if norm_type != "batchnorm" or k not in ("eps", "momentum") or isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise NotImplementedError(f"norm_kwargs.{k}: {v!r} is not built with norm_type {norm_type} (batchnorm takes eps and momentum as "
+                                      "numbers; affine: false, track_running_stats: false and the cumulative average of momentum: null are not built)")
+        out[k] = float(v)
+    if "eps" in out and not (out["eps"] > 0.0 and math.isfinite(out["eps"])):
+        raise ValueError(f"norm_kwargs.eps: {out['eps']!r}, needs a finite positive number")
+    if "momentum" in out and not 0.0 <= out["momentum"] <= 1.0:
+        raise ValueError(f"norm_kwargs.momentum: {out['momentum']!r}, needs a number in [0, 1]")
+    return norm_type, out
+
+
+def refuse_y_hat_cond(y_hat_cond) -> None:
+    if y_hat_cond:
+        raise NotImplementedError("y_hat_cond: true is not built (the reflect-padded y_hat embedding as a further discriminator input)")
+
+
+def check_unet_options(n_layers: int, num_upsample: int, cond_ch: int, input_nc: int) -> None:
+    """What the U-Net discriminator's constructor refuses, as a function of its own for the builder (pure)."""
+    if not 1 <= num_upsample <= n_layers - 1:
+        raise ValueError(f"num_upsample: {num_upsample} with n_layers: {n_layers}, needs 1 <= num_upsample <= n_layers - 1 (every up block adds "
+                         "the body's output of its resolution)")
+    if cond_ch != 3:
+        raise NotImplementedError(f"cond_ch: {cond_ch} is not built: the reference expands the beta embedding with expand_as(x), which runs only "
+                                  "when cond_ch equals the image's 3 channels")
+    if input_nc != 3 + cond_ch:
+        raise ValueError(f"input_nc: {input_nc}, needs 3 + cond_ch = {3 + cond_ch} (the image and the expanded beta embedding)")
+
+
+def make_norm(channels: int, norm_type: str, norm_kwargs: Dict[str, float]) -> nn.Module:
+    if norm_type == "batchnorm":
+        return BatchNorm2d(channels, **norm_kwargs)
+    return ActNorm(channels) if norm_type == "actnorm" else nn.Identity()
+
+
+def weights_init(root: nn.Module) -> None:
+    """taming's weights_init applied over `root` in module order: conv weights ~ N(0, 0.02), BatchNorm weight ~ N(1, 0.02), bias 0."""
+    for m in root.modules():
+        if isinstance(m, Conv2d):
+            nn.init.normal_(m.weight, 0.0, 0.02)
+        elif isinstance(m, BatchNorm2d):
+            nn.init.normal_(m.weight, 1.0, 0.02)
+            nn.init.constant_(m.bias, 0.0)
+
+
+class BetaEmbedding(nn.Module):
+    """oasis_discriminator.py:15-45: the two Fourier encodings and the MLP, under the U-Net's `beta_emb`."""
+
+    def __init__(self, max_beta_1: float, max_beta_2: float, L: int, cond_ch: int, use_pi: bool, include_x: bool):
+        super().__init__()
+        self.embed_1 = FourierEncoding(L=L, max_beta=max_beta_1, use_pi=use_pi, include_x=include_x)
+        self.embed_2 = FourierEncoding(L=L, max_beta=max_beta_2, use_pi=use_pi, include_x=include_x)
+        mlp_in = 2 * (2 * L + 1) if include_x else 2 * 2 * L
+        self.mlp = nn.Sequential(Linear(mlp_in, cond_ch), Act(), Linear(cond_ch, cond_ch))
+
+
+@DISCRIMINATOR_REGISTRY.register()
+class OasisDualBetaCondTamingNLayerDiscriminator(nn.Module):
+    """The OASIS U-Net discriminator (oasis_discriminator.py:67-203) with the reference's state-dict keys: `body.{i}.0` convolutions
+    (k4, s2; `body.{i}.1` their norm from i = 1), `bottleneck.{0,1}` (k3), `up_blocks.{i}.{1,2}` (nearest x2, k3 with bias, norm, then
+    + the body's output of that resolution), `head.{0,2}` (k1) and `beta_emb.mlp.{0,2}`.  The logits lie on a grid of
+    2^(n_layers - num_upsample) pixels.  One quirk is restated literally: the reference expands the beta embedding with
+    `expand_as(x)`, so it runs only when cond_ch equals the image's 3 channels, and input_nc must be 3 + cond_ch."""
+
+    def __init__(self, input_nc: int = 3, ndf: int = 64, n_layers: int = 3, num_upsample: int = 1, out_nc: int = 128, use_actnorm: bool = False,
+                 norm_type: str = "none", norm_kwargs: dict = {}, y_hat_cond: bool = False, y_hat_in_ch=None, y_hat_out_ch=None,
+                 max_beta_1: float = -1.0, max_beta_2: float = -1.0, L: int = 10, cond_ch: int = 8, use_pi: bool = False, include_x: bool = True,
+                 weight_init: bool = True, **kwargs):
+        super().__init__()
+        self.norm_type, self.norm_kwargs = resolve_norm(norm_type, use_actnorm, norm_kwargs)
+        refuse_y_hat_cond(y_hat_cond)
+        n_layers, num_upsample = int(n_layers), int(num_upsample)
+        check_unet_options(n_layers, num_upsample, int(cond_ch), int(input_nc))
+        use_bias = self.norm_type != "batchnorm"
+        norm = lambda ch: make_norm(ch, self.norm_type, self.norm_kwargs)
+        channels = [ndf * min(2 ** i, 8) for i in range(n_layers)]
+        self.body = nn.ModuleList([nn.Sequential(Conv2d(input_nc, channels[0], 4, 2, 1), Act())])
+        for n in range(1, n_layers):
+            self.body.append(nn.Sequential(Conv2d(channels[n - 1], channels[n], 4, 2, 1, bias=use_bias), norm(channels[n]), Act()))
+        self.bottleneck = nn.Sequential(Conv2d(channels[-1], channels[-1], 3, 1, 1, bias=use_bias), norm(channels[-1]), Act())
+        self.up_blocks = nn.ModuleList()
+        for i in range(num_upsample):
+            c_in, c_out = channels[n_layers - 1 - i], channels[n_layers - 2 - i]
+            self.up_blocks.append(nn.Sequential(Act(), Conv2d(c_in, c_out, 3, 1, 1), norm(c_out), Act()))       # index 0: the nearest x2
+        self.head = nn.Sequential(Conv2d(channels[n_layers - 1 - num_upsample], 64, 1, 1, 0), Act(), Conv2d(64, out_nc, 1, 1, 0))
+        self.beta_emb = BetaEmbedding(max_beta_1, max_beta_2, L, cond_ch, use_pi, include_x)
+        self.n_layers, self.num_upsample, self.cond_ch = n_layers, num_upsample, int(cond_ch)
+        self.y_hat_cond = False
+        if weight_init:
+            weights_init(self)
+
+    @property
+    def logit_stride(self) -> int:
+        return 2 ** (self.n_layers - self.num_upsample)
+
+
+def _conv_norm_lrelu(ctx: Ctx, h: Var, conv: Conv2d, norm: nn.Module) -> Var:
+    """conv -> norm -> LeakyReLU(0.2): the activation is fused into the norm's apply pass, or into the conv where there is no norm."""
+    if isinstance(norm, BatchNorm2d):
+        return A.batch_norm(ctx, A.conv(ctx, h, conv), norm, act=ops.ACT_LRELU02)
+    if isinstance(norm, ActNorm):
+        return A.act_norm(ctx, A.conv(ctx, h, conv), norm, act=ops.ACT_LRELU02)
+    return A.conv(ctx, h, conv, act=ops.ACT_LRELU02)
+
+
+def _beta_map(ctx: Ctx, owner, cond_ch: int, x: Var, beta_1, beta_2) -> Var:
+    """The beta embedding [B, cond_ch, 1, 1] broadcast over x's batch and pixels, differentiable."""
     N, _, H, W = x.shape
     dev = x.data.device
-    cond = cond_vector(ctx, D, beta_1, beta_2, dev)                       # [B, cond_ch, 1, 1]
-    zeros = torch.zeros((N, D.cond_ch, H, W), dtype=torch.float32, device=dev)
-    zvec = torch.zeros((cond.shape[0], D.cond_ch, 1, 1), dtype=torch.float32, device=dev)
-    cmap = A.chan_affine(ctx, A.const(zeros), A.const(zvec), cond)        # 0 * (1 + 0) + cond[n][c]: the broadcast, differentiable
-    h = A.cat_channels(ctx, [x, cmap])
+    cond = cond_vector(ctx, owner, beta_1, beta_2, dev)                   # [B, cond_ch, 1, 1]
+    zeros = torch.zeros((N, cond_ch, H, W), dtype=torch.float32, device=dev)
+    zvec = torch.zeros((cond.shape[0], cond_ch, 1, 1), dtype=torch.float32, device=dev)
+    return A.chan_affine(ctx, A.const(zeros), A.const(zvec), cond)        # 0 * (1 + 0) + cond[n][c]
+
+
+def _unet_forward(ctx: Ctx, D: OasisDualBetaCondTamingNLayerDiscriminator, x: Var, beta_1, beta_2) -> Var:
+    if x.shape[1] != D.cond_ch:
+        raise ValueError(f"OASIS U-Net discriminator: images of {x.shape[1]} channels, the beta embedding expands to cond_ch = {D.cond_ch}")
+    h = A.cat_channels(ctx, [x, _beta_map(ctx, D.beta_emb, D.cond_ch, x, beta_1, beta_2)])
+    shortcuts = []
+    for i, blk in enumerate(D.body):
+        h = A.conv(ctx, h, blk[0], act=ops.ACT_LRELU02) if i == 0 else _conv_norm_lrelu(ctx, h, blk[0], blk[1])
+        shortcuts.append(h)
+    h = _conv_norm_lrelu(ctx, h, D.bottleneck[0], D.bottleneck[1])
+    for i, blk in enumerate(D.up_blocks):
+        h = _conv_norm_lrelu(ctx, A.upsample2(ctx, h), blk[1], blk[2])
+        h = A.add(ctx, h, shortcuts[-i - 2])
+    h = A.conv(ctx, h, D.head[0], act=ops.ACT_LRELU02)
+    return A.conv(ctx, h, D.head[2])
+
+
+def discriminator_forward(ctx: Ctx, D: nn.Module, x: Var, beta_1, beta_2) -> Var:
+    """D(x, beta_1, beta_2) on the tape, for either discriminator class.  A normalised one runs in train mode: every call takes its own
+    batch statistics and updates the running ones."""
+    if isinstance(D, OasisDualBetaCondTamingNLayerDiscriminator):
+        return _unet_forward(ctx, D, x, beta_1, beta_2)
+    h = A.cat_channels(ctx, [x, _beta_map(ctx, D, D.cond_ch, x, beta_1, beta_2)])
     h = A.conv(ctx, h, D.main[0], act=ops.ACT_LRELU02)
-    h = A.conv(ctx, h, D.main[2], act=ops.ACT_LRELU02)
-    h = A.conv(ctx, h, D.main[5], act=ops.ACT_LRELU02)
-    h = A.conv(ctx, h, D.main[8], act=ops.ACT_LRELU02)
-    return A.conv(ctx, h, D.main[11])
+    for i in range(2, len(D.main) - 1, 3):
+        h = _conv_norm_lrelu(ctx, h, D.main[i], D.main[i + 1])
+    return A.conv(ctx, h, D.main[-1])

@@ -28,7 +28,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from ..layers import invalidate_weight_caches
+from ..layers import ActNorm, invalidate_weight_caches
 from ..registry import LOSS_REGISTRY, TRAINER_REGISTRY
 from . import autograd as A
 from . import kernels as K
@@ -259,6 +259,10 @@ class DualBetaCondGanDistortionVqCodeTrainer(BetaPairTrainerBase):
         code logits instead of their argmax (hyperprior_dc_vic_model.py:254-260), which lets the image losses reach the estimator; the
         only keyword is `tau` (> 0, default 1).  The draws come from `self.gumbel_gen`, a device generator seeded like the beta sampler."""
         self.model, self.D = model, discriminator
+        if dist is not None and dist.get_world_size() > 1 and any(isinstance(m, ActNorm) for m in discriminator.modules()):
+            # BatchNorm statistics are per rank, as under DDP without SyncBatchNorm; rank 0's buffers are the ones saved
+            raise ValueError("norm_type actnorm cannot train on more than one rank: its data-dependent initialisation (loc and scale from the "
+                             "first batch) would differ per rank")
         dev = next(model.decoder.parameters()).device
         self.device = dev
         # only decoder, vq_estimator, fusion_module are trained (:47-52)
@@ -446,10 +450,15 @@ class DualBetaCondOasisGanDistortionVqFusionTrainer(DualBetaCondGanDistortionVqC
 
     def __init__(self, model, discriminator, *args, **kwargs):
         n_embed = int(model.vq_model.quantize.embedding.weight.shape[0])
-        last = discriminator.main[-1]
+        unet = isinstance(discriminator, nets.OasisDualBetaCondTamingNLayerDiscriminator)
+        last = discriminator.head[-1] if unet else discriminator.main[-1]
         if int(last.out_channels) != n_embed + 1:
             raise ValueError(f"OASIS discriminator: out_nc is {int(last.out_channels)}, the model's codebook needs n_embed + 1 = {n_embed + 1} classes")
-        if int(last.kernel_size) != 3:
+        if unet:
+            if discriminator.logit_stride != 8:
+                raise ValueError(f"OASIS U-Net discriminator: its logits lie on a grid of 2^(n_layers - num_upsample) = {discriminator.logit_stride} "
+                                 "pixels, the VQ tokens on one of 8")
+        elif int(last.kernel_size) != 3:
             raise ValueError("OASIS discriminator: keep_shape must be True so that the logits map is the VQ token grid (H / 8 x W / 8)")
         super().__init__(model, discriminator, *args, **kwargs)
         self.gan_loss = OasisGANLoss(self.w["gan"])

@@ -63,9 +63,8 @@ import torch
 sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dc_vic_amd import BaseConfig, build_comp_model  # noqa: E402
 from dc_vic_amd.parallel import launched_by_a_launcher, pin_rank_cpus, self_launch  # noqa: E402
-from dc_vic_amd.train import DualBetaCondTamingNLayerDiscriminator  # noqa: E402
-from dc_vic_amd.train.build import (DEFAULT_DISCRIMINATOR, build_rd_trainer, build_trainer, choose_gan_trainer, choose_trainer, get_in,  # noqa: E402,F401
-                                    read_gumbel_options)
+from dc_vic_amd.train.build import (build_discriminator, build_rd_trainer, build_trainer, choose_gan_trainer, choose_trainer, get_in,  # noqa: E402,F401
+                                    read_discriminator, read_gumbel_options)
 from dc_vic_amd.train.data import HostFeed, TrainFeed, list_train_images, read_train_dataset  # noqa: E402
 from dc_vic_amd.train.losses import read_loss_section  # noqa: E402
 from dc_vic_amd.train.trainer import DEFAULT_LOSS  # noqa: E402
@@ -194,6 +193,10 @@ def main():
     losses = read_loss_section(opt0)                                       # likewise: every `loss` entry is honoured or refused
     if gan_kind != "rd":
         read_gumbel_options(opt0)                                          # likewise
+        d_read = read_discriminator(opt0)                                  # likewise: the type and every option it does not build
+        if d_read["norm_type"] == "actnorm" and max(a.gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1:
+            raise SystemExit("discriminator.norm_type: actnorm cannot train on more than one rank: its data-dependent initialisation (loc and "
+                             "scale from the first batch) would differ per rank")
     listing = list_training_set(a, opt0)                                   # likewise: the `dataset` section, the folder, its listing
     if a.eval_dataset_root is not None:
         try:                                          # a folder named on the command line must hold PNGs: checked before any GPU work
@@ -232,10 +235,8 @@ def main():
         load_synth_weights(model, 1234)
     else:
         model.load_learned_weight(ckpt_path=a.model_path)
-    dopt = dict(get_in(opt, "discriminator", default=None) or DEFAULT_DISCRIMINATOR)
-    dopt.pop("type", None)
     torch.manual_seed(a.seed)                       # identical D initialisation on every rank
-    D = None if gan_kind == "rd" else DualBetaCondTamingNLayerDiscriminator(**dopt).to(device)     # the rate-distortion trainer has none
+    D, d_line = (None, None) if gan_kind == "rd" else build_discriminator(opt, device)             # the rate-distortion trainer has none
     w_perc = losses["weights"].get("perceptual", DEFAULT_LOSS["perceptual"])
     lpips_state = None
     if a.lpips_path:
@@ -249,7 +250,7 @@ def main():
             print("[train] WARNING: " + msg, file=sys.stderr, flush=True)
     trainer, lines = build_trainer(opt, losses, model, D, dist, a.seed * 100 + rank, lpips_state, a.gan)
     if rank == 0:
-        for line in lines:
+        for line in lines + ([d_line] if d_line else []):
             print("[train] " + line, flush=True)
     start_iter = 0
     if a.resume:

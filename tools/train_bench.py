@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """samples/s of the stage-3 training step (BASELINE config 5: 256x256 crops, batch 8 per GPU, G + D step) -- a SEPARATE metric,
 never mixed into bench.py's headline.  python tools/train_bench.py [--gan {vanilla,oasis} | --stage 1_2 [--distortion {MSELoss,L1Loss,MSSSIMLoss}]] [--batch 8] [--steps 5] [--warmup 2]
-(--gan oasis: the 257-class per-token discriminator of config/dc_vic_oasis.yaml and the OASIS cross-entropy loss; --stage 1_2: the
+[--disc_norm {none,batchnorm,actnorm}] [--disc unet]
+(--disc_norm: the discriminator's normalisation layers, csrc/bn_train.hip; --disc unet: the OASIS U-Net discriminator with --gan oasis; --gan oasis: the 257-class per-token discriminator of config/dc_vic_oasis.yaml and the OASIS cross-entropy loss; --stage 1_2: the
 rate-distortion step of train/rd_trainer.py with config/exp1_stage1_2.yaml's trainer and loss sections, no discriminator); under
 torch.distributed.run it is data-parallel (weak scaling) and reports the aggregate."""
 import argparse
@@ -22,6 +23,8 @@ def main():
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--gan", choices=("vanilla", "oasis"), default="vanilla")
+    p.add_argument("--disc_norm", choices=("none", "batchnorm", "actnorm"), default="none", help="the discriminator's norm_type")
+    p.add_argument("--disc", choices=("patchgan", "unet"), default="patchgan", help="unet: the OASIS U-Net discriminator (needs --gan oasis)")
     p.add_argument("--stage", choices=("3", "1_2"), default="3", help="3: the G + D step (default); 1_2: the rate-distortion step")
     p.add_argument("--distortion", choices=("MSELoss", "L1Loss", "MSSSIMLoss"), default="MSELoss", help="--stage 1_2: distortion_loss.type")
     a = p.parse_args()
@@ -58,7 +61,8 @@ def main():
     dt = time.perf_counter() - t0
     if rank == 0:
         print(json.dumps({"metric": f"training samples/sec, {what} @256x256", "value": world * a.batch * a.steps / dt, "unit": "samples/s",
-                          "gan": a.gan if a.stage == "3" else None, "stage": a.stage, "n_gpus": world, "steps": a.steps, "ms_per_step": 1e3 * dt / a.steps,
+                          "gan": a.gan if a.stage == "3" else None, "disc": a.disc if a.stage == "3" else None,
+                          "disc_norm": a.disc_norm if a.stage == "3" else None, "stage": a.stage, "n_gpus": world, "steps": a.steps, "ms_per_step": 1e3 * dt / a.steps,
                           "batch_per_gpu": a.batch, "dtype": "f32",
                           "data": "synthetic", "lpips": "included, synthetic weights (parity unpinned)", "last_log": log}), flush=True)
     if dist is not None:
@@ -78,10 +82,17 @@ def rd_trainer(m, dist, rank, distortion="MSELoss"):
 
 def gan_trainer(a, m, dev, dist, rank):
     from dc_vic_amd.train import (DualBetaCondGanDistortionVqCodeTrainer, DualBetaCondOasisGanDistortionVqFusionTrainer,
-                                  DualBetaCondTamingNLayerDiscriminator)
+                                  DualBetaCondTamingNLayerDiscriminator, OasisDualBetaCondTamingNLayerDiscriminator)
     torch.manual_seed(0)
-    dkw = dict(out_nc=m.vq_model.quantize.embedding.weight.shape[0] + 1, keep_shape=True) if a.gan == "oasis" else {}
-    D = DualBetaCondTamingNLayerDiscriminator(input_nc=11, n_layers=3, ndf=64, norm_type="none", max_beta_1=3.0, max_beta_2=3.5, **dkw).to(dev)
+    n_cls = m.vq_model.quantize.embedding.weight.shape[0] + 1
+    if a.disc == "unet":
+        if a.gan != "oasis":
+            raise SystemExit("--disc unet needs --gan oasis: its logits are one class column per VQ token")
+        D = OasisDualBetaCondTamingNLayerDiscriminator(input_nc=6, cond_ch=3, n_layers=4, num_upsample=1, ndf=64, out_nc=n_cls, norm_type=a.disc_norm,
+                                                       max_beta_1=3.0, max_beta_2=3.5).to(dev)
+    else:
+        dkw = dict(out_nc=n_cls, keep_shape=True) if a.gan == "oasis" else {}
+        D = DualBetaCondTamingNLayerDiscriminator(input_nc=11, n_layers=3, ndf=64, norm_type=a.disc_norm, max_beta_1=3.0, max_beta_2=3.5, **dkw).to(dev)
     cls = DualBetaCondOasisGanDistortionVqFusionTrainer if a.gan == "oasis" else DualBetaCondGanDistortionVqCodeTrainer
     return cls(m, D, dist=dist, seed=rank)
 

@@ -176,27 +176,40 @@ __global__ __launch_bounds__(Q_THREADS, 4) void conv1x1_dma_kernel(const ConvKAr
             });
         };
         if (has_res) loads(std::integral_constant<int, 0>{}, rv[0]);
-        dcvic_static_for<0, NS>([&](auto s_) {
-            constexpr int sg = decltype(s_)::value, g = sg / 2, r0 = (sg & 1) * SB, mt = g % MT;
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (sg + 1 < NS) { if (has_res) loads(std::integral_constant<int, sg + 1>{}, rv[(sg + 1) & 1]); }
-            __builtin_amdgcn_sched_barrier(0);
-            float v[SB];
-            dcvic_static_for<0, SB>([&](auto r_) {
-                constexpr int r = r0 + decltype(r_)::value;
-                const int cl = (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lane_k;
-                float e = acc[mt][g / MT][r];
-                if (has_bias) e += sbias[cl];
-                e = dcvic_act(e, act);
-                if (has_res) e += rv[sg & 1][r - r0];
-                if (has_aff) e = e * (1.f + sbias[TCv + cl]) + sbias[2 * TCv + cl];
-                v[r - r0] = e;
+        // the activation (none / ReLU: most of the codec's 1x1 layers) and, with it, the presence of a bias are resolved once,
+        // outside the sub-group loop; any other activation keeps the switch per value (one generic body).  GELU stays there on
+        // purpose: as straight-line code hipcc rounds it differently from the switch form the other convolution kernels use, and
+        // a layer must give the same bits whichever kernel the batch size routes it to (tests/test_gpu_conv_direct.py q_64_src3).
+        auto groups = [&](auto act_, auto bias_) {
+            constexpr int ACT = decltype(act_)::value;
+            const bool hb = ACT == DCVIC_ACT_ANY ? has_bias : decltype(bias_)::value;
+            dcvic_static_for<0, NS>([&](auto s_) {
+                constexpr int sg = decltype(s_)::value, g = sg / 2, r0 = (sg & 1) * SB, mt = g % MT;
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (sg + 1 < NS) { if (has_res) loads(std::integral_constant<int, sg + 1>{}, rv[(sg + 1) & 1]); }
+                __builtin_amdgcn_sched_barrier(0);
+                float v[SB];
+                dcvic_static_for<0, SB>([&](auto r_) {
+                    constexpr int r = r0 + decltype(r_)::value;
+                    const int cl = (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lane_k;
+                    float e = acc[mt][g / MT][r];
+                    if (hb) e += sbias[cl];
+                    e = dcvic_act_of<ACT>(e, act);
+                    if (has_res) e += rv[sg & 1][r - r0];
+                    if (has_aff) e = e * (1.f + sbias[TCv + cl]) + sbias[2 * TCv + cl];
+                    v[r - r0] = e;
+                });
+                __builtin_amdgcn_sched_barrier(0);
+                dcvic_static_for<0, SB>([&](auto r_) {
+                    constexpr int r = r0 + decltype(r_)::value;
+                    *reinterpret_cast<float*>(ob + (goff[g] + (unsigned)((r & 3) + 8 * (r >> 2)) * rstep)) = v[r - r0];
+                });
             });
-            __builtin_amdgcn_sched_barrier(0);
-            dcvic_static_for<0, SB>([&](auto r_) {
-                constexpr int r = r0 + decltype(r_)::value;
-                *reinterpret_cast<float*>(ob + (goff[g] + (unsigned)((r & 3) + 8 * (r >> 2)) * rstep)) = v[r - r0];
-            });
+        };
+        dcvic_act_dispatch_some<DCVIC_ACT_NONE, DCVIC_ACT_RELU>(act, [&](auto act_) {
+            if constexpr (decltype(act_)::value == DCVIC_ACT_ANY) groups(act_, std::false_type{});
+            else if (has_bias) groups(act_, std::true_type{});
+            else groups(act_, std::false_type{});
         });
         return;
     }

@@ -33,10 +33,15 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
 }
 
 // One workgroup per (n, group).  The group's cg*HW floats are contiguous in NCHW: 2 reads + 1 write of the group.
-__global__ __launch_bounds__(512) void groupnorm_kernel(const float* __restrict__ x, long long x_bs, float* __restrict__ y,
-                                                        long long y_bs, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, int C, int HW, int groups, float eps,
-                                                        int act, const float* __restrict__ part, int n_pt) {
+// GN_WAVES: the register budget of 8 waves per SIMD (64 VGPRs), which the kernel had while the activation was a switch per value.
+// __launch_bounds__(512) alone only asks for 2 waves per SIMD (128 VGPRs): with the apply loops inside the activation dispatch hipcc
+// 7.2 then takes 65 VGPRs (the unrolled GELU / tanh bodies), i.e. 7 waves, and the HBM-bound launches lose a workgroup per CU; with
+// the attribute it is 61 VGPRs, no scratch (hipcc -Rpass-analysis=kernel-resource-usage; the switch form was 60).
+#define GN_WAVES __attribute__((amdgpu_waves_per_eu(8, 8)))
+__global__ __launch_bounds__(512) GN_WAVES void groupnorm_kernel(const float* __restrict__ x, long long x_bs, float* __restrict__ y,
+                                                                 long long y_bs, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, int C, int HW, int groups, float eps,
+                                                                 int act, const float* __restrict__ part, int n_pt) {
     __shared__ double redd[16];
     const int n = blockIdx.x / groups, g = blockIdx.x % groups;
     const int cg = C / groups;
@@ -75,37 +80,42 @@ __global__ __launch_bounds__(512) void groupnorm_kernel(const float* __restrict_
     const float mean = (float)mean_d;
     const float var = (float)fmax(Q / (double)len - mean_d * mean_d, 0.0);
     const float rstd = 1.0f / sqrtf(var + eps);
-    if (vec) {
-        const float4* x4 = reinterpret_cast<const float4*>(xp);
-        float4* y4 = reinterpret_cast<float4*>(yp);
-        const int hw4 = HW / 4;
-        const long long n4 = len / 4;
-        const int B = blockDim.x;
-        // the channel of element i advances incrementally (no 64-bit division per element); four loads in flight per thread
-        int c = (int)threadIdx.x / hw4, j = (int)threadIdx.x - c * hw4;
-        const int sc = B / hw4, sj = B - sc * hw4;
-        auto put = [&](long long i, float4 v, int cc) {
-            const float ga = gamma[g * cg + cc], be = beta[g * cg + cc];
-            v.x = dcvic_act((v.x - mean) * rstd * ga + be, act);
-            v.y = dcvic_act((v.y - mean) * rstd * ga + be, act);
-            v.z = dcvic_act((v.z - mean) * rstd * ga + be, act);
-            v.w = dcvic_act((v.w - mean) * rstd * ga + be, act);
-            y4[i] = v;
-        };
-        auto step = [&]() { c += sc; j += sj; if (j >= hw4) { j -= hw4; ++c; } };
-        long long i = threadIdx.x;
-        for (; i + 3LL * B < n4; i += 4LL * B) {
-            const float4 v0 = x4[i], v1 = x4[i + B], v2 = x4[i + 2LL * B], v3 = x4[i + 3LL * B];
-            const int c0 = c; step(); const int c1 = c; step(); const int c2 = c; step(); const int c3 = c; step();
-            put(i, v0, c0); put(i + B, v1, c1); put(i + 2LL * B, v2, c2); put(i + 3LL * B, v3, c3);
+    // the apply pass: the launch's activation is resolved ONCE, the loops run inside with the activation as straight-line code (with
+    // the switch per value each of the 16 values of the unrolled loop sat behind a branch chain of its own)
+    dcvic_act_dispatch(act, [&](auto act_) {
+        constexpr int ACT = decltype(act_)::value;
+        if (vec) {
+            const float4* x4 = reinterpret_cast<const float4*>(xp);
+            float4* y4 = reinterpret_cast<float4*>(yp);
+            const int hw4 = HW / 4;
+            const long long n4 = len / 4;
+            const int B = blockDim.x;
+            // the channel of element i advances incrementally (no 64-bit division per element); four loads in flight per thread
+            int c = (int)threadIdx.x / hw4, j = (int)threadIdx.x - c * hw4;
+            const int sc = B / hw4, sj = B - sc * hw4;
+            auto put = [&](long long i, float4 v, int cc) {
+                const float ga = gamma[g * cg + cc], be = beta[g * cg + cc];
+                v.x = dcvic_act_c<ACT>((v.x - mean) * rstd * ga + be);
+                v.y = dcvic_act_c<ACT>((v.y - mean) * rstd * ga + be);
+                v.z = dcvic_act_c<ACT>((v.z - mean) * rstd * ga + be);
+                v.w = dcvic_act_c<ACT>((v.w - mean) * rstd * ga + be);
+                y4[i] = v;
+            };
+            auto step = [&]() { c += sc; j += sj; if (j >= hw4) { j -= hw4; ++c; } };
+            long long i = threadIdx.x;
+            for (; i + 3LL * B < n4; i += 4LL * B) {
+                const float4 v0 = x4[i], v1 = x4[i + B], v2 = x4[i + 2LL * B], v3 = x4[i + 3LL * B];
+                const int c0 = c; step(); const int c1 = c; step(); const int c2 = c; step(); const int c3 = c; step();
+                put(i, v0, c0); put(i + B, v1, c1); put(i + 2LL * B, v2, c2); put(i + 3LL * B, v3, c3);
+            }
+            for (; i < n4; i += B) { put(i, x4[i], c); step(); }
+        } else {
+            for (long long i = threadIdx.x; i < len; i += blockDim.x) {
+                const int c = g * cg + (int)(i / HW);
+                yp[i] = dcvic_act_c<ACT>((xp[i] - mean) * rstd * gamma[c] + beta[c]);
+            }
         }
-        for (; i < n4; i += B) { put(i, x4[i], c); step(); }
-    } else {
-        for (long long i = threadIdx.x; i < len; i += blockDim.x) {
-            const int c = g * cg + (int)(i / HW);
-            yp[i] = dcvic_act((xp[i] - mean) * rstd * gamma[c] + beta[c], act);
-        }
-    }
+    });
 }
 
 extern "C" int dcvic_groupnorm_f32(const float* x, long long x_bs, float* y, long long y_bs, const float* gamma,

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_kernel(const ConvK
         float bv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) bv[r] = C.bias(cg * 16 + 4 * lq + r);
-        dcvic_static_for<0, 2>([&](auto blk_) {
+        auto block = [&](auto blk_, const int a) {                // a: the activation wino22_store applies
             constexpr int blk = decltype(blk_)::value;
             const int oy = C.oy0 + 2 * (2 * th + blk) + (odd ? 1 : 0);
             const bool live = in_x && oy < K.H;
@@ -218,8 +218,14 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_kernel(const ConvK
                 }
                 float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
                 float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
-                wino22_store(y00, y01, y10, y11, bv[r], act, odd, rv[r], ob + (long long)(co0 + r) * HW, live && co0 + r < K.Cout);
+                wino22_store(y00, y01, y10, y11, bv[r], a, odd, rv[r], ob + (long long)(co0 + r) * HW, live && co0 + r < K.Cout);
             }
+        };
+        // the launch's activation resolved once per tile: `a` is a constant for "none" (what the codec launches this kernel with), so
+        // wino22_store's switch folds away there; every other activation keeps it per value in one generic body
+        dcvic_act_dispatch_some<DCVIC_ACT_NONE>(act, [&](auto act_) {
+            const int a = decltype(act_)::value == DCVIC_ACT_ANY ? act : decltype(act_)::value;
+            dcvic_static_for<0, 2>([&](auto blk_) { block(blk_, a); });
         });
 #pragma unroll
         for (int i = 0; i < 16; ++i)
@@ -446,7 +452,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_ups_kernel(const C
         float bv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) bv[r] = C.bias(cg * 16 + 4 * lq + r);
-        dcvic_static_for<0, 2>([&](auto blk_) {
+        auto block = [&](auto blk_, const int a) {                // a: the activation wino22_store applies
             constexpr int blk = decltype(blk_)::value;
             const int oy = C.oy0 + 2 * (2 * th + blk) + (odd ? 1 : 0);
             const bool live = in_x && oy < K.Hfull;
@@ -465,8 +471,12 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv3x3_wino_ups_kernel(const C
                 }
                 float y00 = s0[0] + s0[1], y01 = s0[1] - s0[2];
                 float y10 = s1[0] + s1[1], y11 = s1[1] - s1[2];
-                wino22_store(y00, y01, y10, y11, bv[r], act, odd, rv, ob + (long long)(co0 + r) * HWo, live && co0 + r < K.Cout);
+                wino22_store(y00, y01, y10, y11, bv[r], a, odd, rv, ob + (long long)(co0 + r) * HWo, live && co0 + r < K.Cout);
             }
+        };
+        dcvic_act_dispatch_some<DCVIC_ACT_NONE>(act, [&](auto act_) {   // as in conv3x3_wino_kernel: `a` is a constant for "none"
+            const int a = decltype(act_)::value == DCVIC_ACT_ANY ? act : decltype(act_)::value;
+            dcvic_static_for<0, 2>([&](auto blk_) { block(blk_, a); });
         });
 #pragma unroll
         for (int i = 0; i < WU_NPOS; ++i)

@@ -6,7 +6,8 @@ Drop-in mirror of the reference's model classes and builders:
   src/models/comp_model/base_model.py:16-189 (BaseModel),
   src/models/comp_model/hyperprior_vic_model.py:30-534 (HyperpriorVicModel),
   src/models/comp_model/hyperprior_dc_vic_model.py:25-483 (HyperpriorDualCondVicModel),
-  src/models/comp_model/hyperprior_charm_dc_vic_model.py:16-91 (HyperpriorCharmDualCondVicModel).
+  src/models/comp_model/hyperprior_charm_dc_vic_model.py:16-91 (HyperpriorCharmDualCondVicModel),
+  src/models/comp_model/hyperprior_charm_vic_model.py:14-52 (HyperpriorCharmVicModel, the unconditioned model of stage 1-1).
 Same class names / registry keys / method names / state-dict keys / bitstream; inference only.
 Differences by design (MI355X-first):
   * everything, including hyper-decoder + CHARM, stays on the GPU on both sides (kernels are
@@ -29,7 +30,7 @@ import torch.nn as nn
 from . import ops
 from .charm import Minnen20CharmContextModel  # noqa: F401  (registers)
 from .codec_utils import HeaderHandler
-from .elic import ElicDualBetaFtFeatFusionDecoder, ElicDualBetaFtVqScEncoder  # noqa: F401
+from .elic import ElicDualBetaFtFeatFusionDecoder, ElicDualBetaFtVqScEncoder, ElicFeatFusionDecoder, ElicVqCatScEncoder  # noqa: F401
 from .entropy import EntropyBottleneck, GaussianMeanScaleConditional, get_scale_table, host_threads
 from .fusion import build_vq_fusion_module
 from .hyperprior import Minnen20HyperDecoder, Minnen20HyperEncoder  # noqa: F401
@@ -304,12 +305,16 @@ class BaseModel(nn.Module):
         invalidate_weight_caches(self)
 
     # base_model.py:106-130
-    def load_learned_weight(self, ckpt_path: str, strict: bool = False) -> None:
+    def load_learned_weight(self, ckpt_path: str, strict: bool = False) -> Dict[str, List[str]]:
+        """-> dict(loaded, missing, unexpected): the keys of the checkpoint that were loaded, the model's keys it lacks (they keep the
+        values they have) and its keys the model lacks (dropped); with strict both must be empty."""
         ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
         state_dict = ckpt["comp_model"]
         new_sd = OrderedDict((k[7:] if k.startswith("module.") else k, v) for k, v in state_dict.items())
+        model_dict = self.state_dict()
+        report = dict(loaded=[k for k in new_sd if k in model_dict], missing=[k for k in model_dict if k not in new_sd],
+                      unexpected=[k for k in new_sd if k not in model_dict])
         if not strict:
-            model_dict = self.state_dict()
             model_dict.update({k: v for k, v in new_sd.items() if k in model_dict})
             self.load_state_dict(model_dict)
         else:
@@ -317,6 +322,7 @@ class BaseModel(nn.Module):
         for m in self.children():
             if isinstance(m, EntropyBottleneck):
                 m.update(force=False)
+        return report
 
     def codec_setup(self):
         raise NotImplementedError()
@@ -504,6 +510,24 @@ class HyperpriorVicModel(BaseModel):
                 ops.copy_window(out[:, :, t:b, l:r], o[:, :, t - _y0:b - _y0, l - _x0:r - _x0])
         return out
 
+    # ------------------------------------------------------------------ entropy stage
+    def _entropy_encode_side(self, y: Tensor, want_symbols: bool):
+        """hyper-encoder -> z symbols / z_hat / z bits -> hyper-decoder -> CHARM (all on the GPU)."""
+        N = y.shape[0]
+        z = self.hyperencoder(y)
+        bits_z = torch.zeros(N, dtype=torch.float32, device=y.device)
+        bits_y = torch.zeros(N, dtype=torch.float32, device=y.device)
+        z_hat = torch.empty_like(z)
+        z_lik = torch.empty_like(z)
+        z_sym = torch.empty(z.shape, dtype=torch.int32, device=y.device) if want_symbols else None
+        ops.eb_rate(z, self.entropy_model_z.packs(), z_hat, z_sym, z_lik, bits_z)
+        hyper_out = self.hyperdecoder(z_hat)
+        r = self._run_context(y, hyper_out, want_symbols, bits_y)
+        return dict(z=z, z_hat=z_hat, z_likelihood=z_lik, z_symbols=z_sym, bits_z=bits_z, bits_y=bits_y, hyper_out=hyper_out, **r)
+
+    def _run_context(self, y, hyper_out, want_symbols, bits_y):
+        raise NotImplementedError("only the CHARM variants (HyperpriorCharmVicModel, HyperpriorCharmDualCondVicModel) are shipped")
+
     def codec_setup(self):
         """hyperprior_dc_vic_model.py:65-89: build the integer CDF tables; strides are properties of the
         architecture (4 stride-2 encoder stages -> y_stride 16, 2 more in the hyper-encoder -> 64)."""
@@ -531,24 +555,6 @@ class HyperpriorDualCondVicModel(HyperpriorVicModel):
         if self.use_selected_beta_pairs:
             assert isinstance(self.selected_beta_rate, list) and isinstance(self.selected_beta_vq, list)
             assert len(self.selected_beta_rate) == len(self.selected_beta_vq)
-
-    # ------------------------------------------------------------------ entropy stage
-    def _entropy_encode_side(self, y: Tensor, want_symbols: bool):
-        """hyper-encoder -> z symbols / z_hat / z bits -> hyper-decoder -> CHARM (all on the GPU)."""
-        N = y.shape[0]
-        z = self.hyperencoder(y)
-        bits_z = torch.zeros(N, dtype=torch.float32, device=y.device)
-        bits_y = torch.zeros(N, dtype=torch.float32, device=y.device)
-        z_hat = torch.empty_like(z)
-        z_lik = torch.empty_like(z)
-        z_sym = torch.empty(z.shape, dtype=torch.int32, device=y.device) if want_symbols else None
-        ops.eb_rate(z, self.entropy_model_z.packs(), z_hat, z_sym, z_lik, bits_z)
-        hyper_out = self.hyperdecoder(z_hat)
-        r = self._run_context(y, hyper_out, want_symbols, bits_y)
-        return dict(z=z, z_hat=z_hat, z_likelihood=z_lik, z_symbols=z_sym, bits_z=bits_z, bits_y=bits_y, hyper_out=hyper_out, **r)
-
-    def _run_context(self, y, hyper_out, want_symbols, bits_y):
-        raise NotImplementedError("only the CHARM variant (HyperpriorCharmDualCondVicModel) is shipped")
 
     # hyperprior_dc_vic_model.py:120-170 (inference branch: betas must be given)
     def data_preprocess(self, real_images: Tensor, vq_indices: Optional[Tensor] = None, beta_rate=None, beta_vq=None,
@@ -746,8 +752,10 @@ class HyperpriorDualCondVicModel(HyperpriorVicModel):
         return self.decompress_batch([string_list])
 
 
-@MODEL_REGISTRY.register()
-class HyperpriorCharmDualCondVicModel(HyperpriorDualCondVicModel):
+class _CharmEntropy:
+    """What the two CHARM models share (hyperprior_charm_vic_model.py:14-52, hyperprior_charm_dc_vic_model.py:16-56): the context model
+    among the sub-networks and the entropy side through it."""
+
     def _build_subnets(self) -> None:
         super()._build_subnets()
         self.context_model = build_subnet(self.opt["subnet"]["context_model"], "context_model")
@@ -755,18 +763,80 @@ class HyperpriorCharmDualCondVicModel(HyperpriorDualCondVicModel):
     def _run_context(self, y, hyper_out, want_symbols, bits_y):
         return self.context_model.run(y, hyper_out, self.entropy_model_y, want_likelihood=True, want_symbols=want_symbols, bits_out=bits_y)
 
-    # hyperprior_charm_dc_vic_model.py:24-56
     def estimate_entropy(self, y: Tensor, is_train: bool = False):
         if is_train:
             raise NotImplementedError("dc_vic_amd implements the inference path only")
-        e = self._entropy_encode_side(y, want_symbols=False)
+        return self._entropy_dict(y, self._entropy_encode_side(y, want_symbols=False))
+
+    @staticmethod
+    def _entropy_dict(y: Tensor, e: Dict) -> Dict:
+        """estimate_entropy's keys from _entropy_encode_side's: in eval mode both likelihoods are the quantised one."""
         return {"quantized_code": {"y": e["y_hat"], "z": e["z_hat"]}, "latent_code": {"y": y, "z": e["z"]},
                 "likelihoods": {"y": e["y_likelihood"], "z": e["z_likelihood"]},
                 "q_likelihoods": {"y": e["y_likelihood"], "z": e["z_likelihood"]}}
 
+
+@MODEL_REGISTRY.register()
+class HyperpriorCharmDualCondVicModel(_CharmEntropy, HyperpriorDualCondVicModel):
     # hyperprior_charm_dc_vic_model.py:83-91
     def _decompress_entropy(self, z_strs, y_strs, zH: int, zW: int):
         z_hat = self.entropy_model_z.decompress(list(z_strs), (zH, zW))
         hyper_out = self.hyperdecoder(z_hat)
         y_hat, _ = self.context_model.forward_decompress(list(y_strs), hyper_out, self.entropy_model_y)
         return y_hat, z_hat
+
+
+@MODEL_REGISTRY.register()
+class HyperpriorCharmVicModel(_CharmEntropy, HyperpriorVicModel):
+    """hyperprior_charm_vic_model.py over hyperprior_vic_model.py: the unconditioned model stage 1-1 trains (ElicVqCatScEncoder,
+    ElicFeatFusionDecoder: no beta anywhere).  Inference here, training mode on the tape (train/nets.py); the reference has no
+    compress / decompress for this class, nor has this one."""
+
+    def _build_subnets(self) -> None:
+        if _get(self.opt["subnet"], "residual_predictor"):
+            raise NotImplementedError("Residual Predictor is not available yet in HypepriorCharmModel.")      # the reference's words (:19-20)
+        super()._build_subnets()
+
+    # hyperprior_vic_model.py:84-135 (run_model = data_preprocess, forward, data_postprocess)
+    @torch.no_grad()
+    def run_model(self, real_images: Tensor, is_train: bool = False, vq_indices=None, fusion_w: Optional[float] = None,
+                  run_vq_decoder: bool = True, fix_entropy_models: bool = False) -> Dict:
+        """The reference's keywords and no others: a beta here is a caller's mistake, not something to drop silently."""
+        if is_train:
+            raise NotImplementedError("dc_vic_amd implements the inference path only")
+        if not run_vq_decoder:
+            raise NotImplementedError("run_vq_decoder: false is not built")
+        N, _, H, W = real_images.shape
+        x = self.img_preprocess(real_images, is_train=False)
+        gt_vq_latent, gt_vq_indices, feat = self.vq_encode(x, vq_indices, want_feat=True)
+        y = self.comp_encode(x, gt_vq_latent, gt_vq_indices, feat=feat)
+        e = self._entropy_encode_side(y, want_symbols=False)
+        y_hat, z_hat = e["y_hat"], e["z_hat"]
+        if max(x.shape[2:]) > SPLIT_DECODE_RESOLUTION:
+            fake = self.decode_split(y_hat, 1.0, beta_rate=None, beta_vq=None)
+            out_idx = torch.zeros_like(gt_vq_indices)
+            logits = embed = None
+            vq_acc = 0.0
+        else:
+            fake, out_idx, logits, embed = self._decode(y_hat, 1.0, None, None, want_logits=True, want_embed=True)
+            vq_acc = float((out_idx.cpu() == gt_vq_indices.cpu()).float().mean())
+        bpp = (e["bits_y"].double().sum() + e["bits_z"].double().sum()).item() / (N * H * W)          # as the dual model's run_model
+        return dict(real_images=ops.crop_clamp(x, H, W), fake_images=ops.crop_clamp(fake, H, W), y_hat=y_hat, z_hat=z_hat,
+                    out_vq_latent=embed, gt_vq_latent=gt_vq_latent, out_vq_logits=logits, gt_vq_indices=gt_vq_indices, vq_accuracy=vq_acc,
+                    **self._entropy_dict(y, e), y_likelihood=e["y_likelihood"], z_likelihood=e["z_likelihood"], bpp=bpp,
+                    y_q_likelihood=e["y_likelihood"], z_q_likelihood=e["z_likelihood"], qbpp=bpp, out_vq_indices=out_idx,
+                    bits_per_image=(e["bits_y"] + e["bits_z"]))
+
+    # hyperprior_vic_model.py:486-514
+    @torch.no_grad()
+    def validation(self, images: Sequence[Tensor], max_sample_size: int = 100) -> List[Dict]:
+        """One row {idx, bpp, psnr, ms_ssim, vq_acc} per image of `images` ([1, 3, H, W] in [-1, 1], at most max_sample_size)."""
+        from . import metrics
+        rows = []
+        for idx, x in enumerate(list(images)[:max_sample_size]):
+            if x.dim() != 4 or x.shape[0] != 1:
+                raise ValueError(f"validation: image {idx} has shape {tuple(x.shape)}, expected [1, 3, H, W]")
+            out = self.run_model(x, is_train=False)
+            ms, psnr = metrics.ms_ssim_psnr(out["real_images"], out["fake_images"])
+            rows.append(dict(idx=idx + 1, bpp=float(out["bpp"]), psnr=float(psnr[0]), ms_ssim=float(ms[0]), vq_acc=float(out["vq_accuracy"])))
+        return rows

@@ -290,3 +290,104 @@ class ElicDualBetaFtFeatFusionDecoder(_BetaCond):
             if len(fusion_feat_dict) == len(query):
                 break
         return feat_1, fusion_feat_dict
+
+
+@ENCODER_REGISTRY.register()
+class ElicVqCatScEncoder(nn.Module):
+    """elic_insert_encoder.py:54-104: the encoder of the unconditioned stage 1-1 model, ElicDualBetaFtVqScEncoder's layers without
+    `beta_ft_list` and `mlp`.  `beta_1` / `beta_2` are accepted and must be None: the shared model code passes them by keyword."""
+
+    def __init__(self, in_ch: int = 3, out_ch: int = 192, main_ch: int = 192, block_mid_ch: int = 192, num_blocks: int = 3,
+                 res_in_res: bool = False, input_feat_ch: int = 5, proj_init: bool = True, proj_init_std: float = 0.02, proj_pos: str = "conv3"):
+        super().__init__()
+        if proj_pos not in ("conv3", "conv4"):
+            raise ValueError(f"proj_pos: {proj_pos!r} is unknown, expected conv3 or conv4")
+        if proj_pos == "conv4":
+            raise NotImplementedError("proj_pos: conv4 is not built: the VQ feature lies on the H/8 grid of conv3's output, conv4's lies on H/16, "
+                                      "so the reference's concatenation cannot run with this VQGAN; use conv3")
+        self.conv1 = Conv2d(in_ch, main_ch, 5, 2, 2)
+        self.block1 = ResidualBottleneckBlocks(main_ch, block_mid_ch, num_blocks, res_in_res)
+        self.conv2 = Conv2d(main_ch, main_ch, 5, 2, 2)
+        self.block2 = ResidualBottleneckBlocks(main_ch, block_mid_ch, num_blocks, res_in_res)
+        self.attn2 = ChengNLAM(main_ch)
+        self.conv3 = Conv2d(main_ch, main_ch, 5, 2, 2)
+        self.block3 = ResidualBottleneckBlocks(main_ch, block_mid_ch, num_blocks, res_in_res)
+        self.conv4 = Conv2d(main_ch, out_ch, 5, 2, 2)
+        self.attn4 = ChengNLAM(out_ch)
+        self.num_downscale = 4
+        self.projection = Conv2d(main_ch + input_feat_ch, main_ch, 3, 1, 1)
+        if proj_init:
+            nn.init.constant_(self.projection.bias, 0.0)
+            nn.init.trunc_normal_(self.projection.weight, std=proj_init_std, a=-2.0 * proj_init_std, b=2.0 * proj_init_std)   # as train/init.py cuts it
+        self.proj_init, self.proj_init_std = bool(proj_init), float(proj_init_std)
+        self.input_vq_latent = True
+        self.proj_pos = proj_pos
+
+    def forward(self, x: Tensor, feat: Tensor, beta_1=None, beta_2=None) -> Tensor:
+        _refuse_betas(self, beta_1, beta_2)
+        x = self.block1(self.conv1(x))
+        x = self.attn2(self.block2(self.conv2(x)))
+        x = self.conv3(x)
+        x = self.projection([feat, x], res=x)          # x + conv3x3(cat[feat, x])   (run_projection)
+        x = self.block3(x)
+        return self.attn4(self.conv4(x))
+
+
+def _refuse_betas(owner, beta_1, beta_2) -> None:
+    if beta_1 is not None or beta_2 is not None:
+        raise ValueError(f"{type(owner).__name__} is unconditioned: beta_1 / beta_2 must be None, got {beta_1!r} / {beta_2!r}")
+
+
+@DECODER_REGISTRY.register()
+class ElicFeatFusionDecoder(nn.Module):
+    """elic_feat_decoder.py:75-124 (get_feats only; forward raises as the dual class's does): ElicDualBetaFtFeatFusionDecoder's
+    layers without `beta_ft_list`, `mlp` and `init_fuse`."""
+
+    def __init__(self, fusion_layer_dict: Dict[str, str], feat_layer_name: str, in_ch: int = 192, out_ch: int = 3,
+                 main_ch: int = 192, block_mid_ch: int = 192, num_blocks: int = 3, use_tanh: bool = True,
+                 pixel_shuffle: bool = False, res_in_res: bool = False):
+        super().__init__()
+        assert not pixel_shuffle and not res_in_res
+        self.use_tanh = use_tanh
+        up = lambda i, o: ConvTranspose2d(i, o, 5, 2, 2, 1)
+        self.attn1 = ChengNLAM(in_ch)
+        self.conv1 = up(in_ch, main_ch)
+        self.block1 = ResidualBottleneckBlocks(main_ch, block_mid_ch, num_blocks)
+        self.conv2 = up(main_ch, main_ch)
+        self.attn2 = ChengNLAM(main_ch)
+        self.block2 = ResidualBottleneckBlocks(main_ch, block_mid_ch, num_blocks)
+        self.conv3 = up(main_ch, main_ch)
+        self.block3 = ResidualBottleneckBlocks(main_ch, block_mid_ch, num_blocks)
+        self.conv4 = up(main_ch, out_ch)     # present in checkpoints, never executed (get_feats breaks first)
+        self.layer_names = ["attn1", "conv1", "block1", "conv2", "attn2", "block2", "conv3", "block3", "conv4"]
+        self.feat_layer = feat_layer_name
+        assert self.feat_layer in self.layer_names
+        self.fusion_layer_dict = dict(fusion_layer_dict)
+        for k in self.fusion_layer_dict:
+            assert k in self.layer_names
+
+    def forward(self, x):
+        raise NotImplementedError()
+
+    def get_feats(self, x: Tensor, beta_1=None, beta_2=None, feat_out: Optional[Dict[str, Tensor]] = None):
+        """Returns (feat_1, {fusion key: feature}); `feat_out` as in ElicDualBetaFtFeatFusionDecoder.get_feats."""
+        _refuse_betas(self, beta_1, beta_2)
+        fusion_feat_dict: Dict[str, Tensor] = {}
+        query = list(self.fusion_layer_dict.keys())
+        feat_1 = None
+        for name in self.layer_names:
+            layer = getattr(self, name)
+            dst = None
+            if feat_out is not None and name in self.fusion_layer_dict:
+                dst = feat_out.get(self.fusion_layer_dict[name])
+            if isinstance(layer, ResidualBottleneckBlocks):
+                x = layer(x, out=dst)
+            else:
+                x = layer(x)
+            if name == self.feat_layer:
+                feat_1 = x
+            if name in query:
+                fusion_feat_dict[self.fusion_layer_dict[name]] = x
+            if len(fusion_feat_dict) == len(query):
+                break
+        return feat_1, fusion_feat_dict

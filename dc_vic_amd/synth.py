@@ -169,11 +169,20 @@ def full_synth_state_dict(seed: int = 1234) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def is_conditioning_key(name: str) -> bool:
+    """True for the beta-conditioning tensors of the dual-conditioned encoder and decoder (`beta_ft_list`, `mlp`, `init_fuse`): the
+    state-dict keys the unconditioned stage 1-1 model lacks."""
+    return name.startswith(("encoder.", "decoder.")) and name.split(".")[1] in ("beta_ft_list", "mlp", "init_fuse")
+
+
 def load_synth_weights(model, seed: int = 1234) -> Dict[str, torch.Tensor]:
     """Load the deterministic synthetic weights into a dc_vic_amd comp model (in place) and return
-    the CPU state dict that was loaded (the oracle consumes the same dict)."""
+    the CPU state dict that was loaded (the oracle consumes the same dict).  The unconditioned model (no `beta_ft_list`) gets the
+    dual-conditioned state without its conditioning keys: every tensor the two models share has the same name, shape and bits."""
     sd = full_synth_state_dict(seed)
     own = model.state_dict()
+    if not hasattr(model.encoder, "beta_ft_list"):
+        sd = {k: v for k, v in sd.items() if not is_conditioning_key(k)}
     missing = [k for k in sd if k not in own]
     if missing:
         raise KeyError(f"synthetic weights name parameters the model lacks: {missing[:5]}")

@@ -119,7 +119,7 @@ def sample_loss_weights(loss_weight: float, reduction: str, N: int, elems_per_im
 
 # ---------------------------------------------------------------------------------------------------- the YAML's `loss` section
 # the reference's trainers with a rate term and per-sample beta weights (config/exp1_stage1_1.yaml, exp1_stage1_2.yaml): the second is
-# train/rd_trainer.py, the first is not built and train/build.py's choose_trainer refuses it by `trainer.type`.  Their `rate_loss` entry and
+# train/rd_trainer.py, and so is the first, over the unconditioned model (train/build.py's choose_trainer).  Their `rate_loss` entry and
 # `reduction: none` are read for them here; in a GAN-stage config both are refused.
 RATE_DISTORTION_TRAINERS = ("RateDistortionVqCodeTrainer", "DualBetaCondRateDistortionVqCodeTrainer")
 _ENTRIES = ("distortion_loss", "perceptual_loss", "gan_loss", "code_distortion_loss", "code_ce_loss", "rate_loss")

@@ -68,20 +68,37 @@ def nlam(ctx: Ctx, m: ChengNLAM, x: Var) -> Var:
     return A.nlam_gate(ctx, x, t, A.conv(ctx, a, m.conv))
 
 
-def decoder_get_feats(ctx: Ctx, dec, y_hat, beta_1, beta_2):
-    """ElicDualBetaFtFeatFusionDecoder.get_feats with a tape.  y_hat is a Tensor (a constant: the GAN stages run the entropy side under
-    no_grad) or a Var (estimate_entropy_train's quantized_code.y: the gradient that arrives on it continues into the analysis side)."""
+def _beta_ft(ctx: Ctx, owner, beta_1, beta_2, device):
+    """The beta-FT of `owner` (an ELIC encoder or decoder) as a function (scale/shift module, v) -> v * (1 + s) + t, with the cond
+    vector recorded once.  An unconditioned owner (no `beta_ft_list`: ElicVqCatScEncoder, ElicFeatFusionDecoder) gets the identity and
+    nothing is recorded: no cond_vector, no beta_vectors, no chan_affine."""
+    if not hasattr(owner, "beta_ft_list"):
+        if beta_1 is not None or beta_2 is not None:
+            raise ValueError(f"{type(owner).__name__} is unconditioned: beta_1 / beta_2 must be None, got {beta_1!r} / {beta_2!r}")
+        return None
+    cond = cond_vector(ctx, owner, beta_1, beta_2, device)
+
+    def ft(m: BetaScaleShiftModule, v: Var, add_x: bool = False) -> Var:
+        s, t = beta_vectors(ctx, m, cond)
+        return A.chan_affine(ctx, v, s, t, add_x=add_x)
+    return ft
+
+
+def decoder_get_feats(ctx: Ctx, dec, y_hat, beta_1=None, beta_2=None):
+    """ElicDualBetaFtFeatFusionDecoder.get_feats, or the unconditioned ElicFeatFusionDecoder's (betas None), with a tape.  y_hat is a Tensor
+    (a constant: the GAN stages run the entropy side under no_grad) or a Var (estimate_entropy_train's quantized_code.y: the gradient that
+    arrives on it continues into the analysis side)."""
     x = y_hat if isinstance(y_hat, Var) else A.const(y_hat)
-    cond = cond_vector(ctx, dec, beta_1, beta_2, x.data.device)
-    s0, t0 = beta_vectors(ctx, dec.init_fuse, cond)
-    x = A.chan_affine(ctx, x, s0, t0, add_x=True)                         # init_fuse(x, c) + x   (:343)
+    ft = _beta_ft(ctx, dec, beta_1, beta_2, x.data.device)
+    if ft is not None:
+        x = ft(dec.init_fuse, x, add_x=True)                              # init_fuse(x, c) + x   (:343)
     feats: Dict[str, Var] = {}
     query = list(dec.fusion_layer_dict.keys())
     feat_1 = None
     for li, name in enumerate(dec.layer_names):
         layer = getattr(dec, name)
-        s, t = beta_vectors(ctx, dec.beta_ft_list[li], cond)
-        x = A.chan_affine(ctx, x, s, t)
+        if ft is not None:
+            x = ft(dec.beta_ft_list[li], x)
         if isinstance(layer, ResidualBottleneckBlocks):
             x = bottleneck_blocks(ctx, layer, x)
         elif isinstance(layer, ChengNLAM):
@@ -98,14 +115,12 @@ def decoder_get_feats(ctx: Ctx, dec, y_hat, beta_1, beta_2):
 
 
 # ------------------------------------------------------------------------------------------- analysis side
-def encoder_forward(ctx: Ctx, enc, x: Tensor, feat: Tensor, beta_1, beta_2) -> Var:
-    """ElicDualBetaFtVqScEncoder.forward with a tape: the image and the VQ feature (latent | one-hot indices) are constants, the
-    beta vectors are per sample ([B] tensors) or shared (scalars); beta-FT follows each layer."""
-    cond = cond_vector(ctx, enc, beta_1, beta_2, x.device)
-
-    def ft(i: int, v: Var) -> Var:
-        s, t = beta_vectors(ctx, enc.beta_ft_list[i], cond)
-        return A.chan_affine(ctx, v, s, t)
+def encoder_forward(ctx: Ctx, enc, x: Tensor, feat: Tensor, beta_1=None, beta_2=None) -> Var:
+    """ElicDualBetaFtVqScEncoder.forward, or the unconditioned ElicVqCatScEncoder's (betas None), with a tape: the image and the VQ
+    feature (latent | one-hot indices) are constants, the beta vectors are per sample ([B] tensors) or shared (scalars); beta-FT follows
+    each layer of the conditioned class."""
+    beta_ft = _beta_ft(ctx, enc, beta_1, beta_2, x.device)
+    ft = (lambda i, v: v) if beta_ft is None else (lambda i, v: beta_ft(enc.beta_ft_list[i], v))
     h = ft(0, A.conv(ctx, A.const(x), enc.conv1))
     h = ft(1, bottleneck_blocks(ctx, enc.block1, h))
     h = ft(2, A.conv(ctx, h, enc.conv2))
@@ -206,11 +221,11 @@ def estimate_entropy_train(ctx: Ctx, model, y: Var, noise_y: Tensor, noise_z: Te
             "symbols": {"y": r["symbols"], "z": z_sym}, "hyper_out": hyper_out}
 
 
-def analysis_forward(ctx: Ctx, model, x: Tensor, beta_rate, beta_vq, vq_indices: Optional[Tensor] = None, noise_y: Optional[Tensor] = None,
+def analysis_forward(ctx: Ctx, model, x: Tensor, beta_rate=None, beta_vq=None, vq_indices: Optional[Tensor] = None, noise_y: Optional[Tensor] = None,
                      noise_z: Optional[Tensor] = None, generator: Optional[torch.Generator] = None, weights: Optional[Tensor] = None,
                      scale: float = 1.0) -> Dict:
     """The analysis side of one training step on a preprocessed batch x [N, 3, H, W] (sides multiples of 64): the no-grad VQ encode,
-    the beta-conditioned encoder and estimate_entropy_train.  Without explicit noise, U(-0.5, 0.5) is drawn on the device from
+    the encoder (beta-conditioned, or unconditioned with both betas None) and estimate_entropy_train.  Without explicit noise, U(-0.5, 0.5) is drawn on the device from
     `generator` (as entropy._train_noise does).  -> estimate_entropy_train's dict plus gt_vq_latent / gt_vq_indices."""
     from ..entropy import _train_noise
     if x.shape[2] % 64 or x.shape[3] % 64:
@@ -318,7 +333,7 @@ def fusion_decode(ctx: Ctx, fm, vq_dec, z: Var, cond_feats: Dict[str, Var], w: f
     return A.conv(ctx, h, vq_dec.conv_out)
 
 
-def synthesis_forward(ctx: Ctx, model, y_hat, beta_rate, beta_vq, gumbel: Optional[Tuple[Tensor, float]] = None) -> Dict:
+def synthesis_forward(ctx: Ctx, model, y_hat, beta_rate=None, beta_vq=None, gumbel: Optional[Tuple[Tensor, float]] = None) -> Dict:
     """The synthesis side of a training step, analysis_forward's counterpart (hyperprior_dc_vic_model.py:240-274): decoder features of y_hat
     (Tensor or Var, see decoder_get_feats), the VQ estimator, its logits' argmax through the post_quant_conv LUT, the fusion decoder.  With
     `gumbel` = (noise, tau), the caller's draw, the decoder reads the hard Gumbel-softmax sample's latent (:254-260); out_vq_indices stays the argmax."""

@@ -105,6 +105,25 @@ class MultiStepLR:
         self.last_epoch += 1
 
 
+class LinearWarmupScheduler:
+    """build_optimizer_scheduler.py:13-24: lr(k) = base_lr * (warmup_factor * (1 - k / warmup_iters) + k / warmup_iters) for
+    k < warmup_iters steps taken, base_lr from then on; the expression is the reference's, operation by operation."""
+
+    def __init__(self, base_lr: float, warmup_iters: int, warmup_factor: float):
+        if isinstance(warmup_iters, bool) or not isinstance(warmup_iters, int) or warmup_iters < 0:
+            raise ValueError(f"warmup_iters: {warmup_iters!r} is not an integer >= 0")
+        self.base_lr, self.warmup_iters, self.warmup_factor, self.last_epoch = base_lr, warmup_iters, float(warmup_factor), 0
+
+    def lr(self) -> float:
+        if self.last_epoch < self.warmup_iters:
+            alpha = float(self.last_epoch) / self.warmup_iters
+            return self.base_lr * (self.warmup_factor * (1 - alpha) + alpha)
+        return self.base_lr
+
+    def step(self) -> None:
+        self.last_epoch += 1
+
+
 class Adam:
     """torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8) on a ParamGroup's flat buffers."""
 

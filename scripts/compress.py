@@ -98,6 +98,9 @@ def main():
         torch.cuda.set_device(torch.device(device))      # `-d cuda:1` makes cuda:1 the current device (kernels launch there)
     overrides["is_train"] = False
     opt = BaseConfig.fromfile(args.config_path, overrides)
+    if opt["model"]["type"] == "HyperpriorCharmVicModel":
+        raise SystemExit("model.type: HyperpriorCharmVicModel has no bitstream: the unconditioned stage 1-1 model has neither compress nor "
+                         "decompress (in the reference as here); train stage 1-2 from it and compress with that model")
     ck = opt["subnet"]["vq_model"].get("ckpt_path")
     if ck and not os.path.exists(ck):
         print(f"[compress] VQGAN checkpoint {ck} not found: skipping (weights must come from --model_path)", file=sys.stderr)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Stage-3 / 1-3 GAN training and stage 1-2 rate-distortion training of DC-VIC on MI355X -- counterpart of the reference's scripts/train.py:16-27 +
+"""Stage-3 / 1-3 GAN training and stage 1-1 / 1-2 rate-distortion training of DC-VIC on MI355X -- counterpart of the reference's scripts/train.py:16-27 +
 src/trainer/base_trainer.py:130-152 (train_loop) for the `DualBetaCondGanDistortionVqCodeTrainer` of config/exp1_stage3.yaml.
 
     python scripts/train.py CONFIG [--model_path CKPT | --synthetic_weights] [--dataset_root DIR | --synthetic_data]
@@ -46,8 +46,15 @@ Rate-distortion (config/exp1_stage1_2.yaml): `trainer.type: DualBetaCondRateDist
 (choose_trainer, in front of choose_gan_trainer): the whole model but the VQGAN trains on rate + distortion + perceptual + code losses with
 per-sample weights exp(beta) or beta + offset (`trainer.beta_policy`, `beta_offset`, `sample_beta_batch`; `loss.rate_loss` and the
 `reduction: none` entries are read), `optim.aux_optimizer.lr` drives the entropy bottleneck's quantiles.  No discriminator is built and
-no discriminator_* file is written or read (the trainer's checkpoint_modules names the files of a checkpoint); --gan with such a config is an error, and so is the stage 1-1 `RateDistortionVqCodeTrainer`
-(an unconditioned model that is not built).  A stage 1-2 run starts from a dual-conditioned checkpoint (--model_path) or synthetic weights.
+no discriminator_* file is written or read (the trainer's checkpoint_modules names the files of a checkpoint); --gan with such a config is an error.
+Stage 1-1 (config/exp1_stage1_1.yaml, config/dc_vic_synthetic_stage1_1.yaml): `trainer.type: RateDistortionVqCodeTrainer` over `model.type:
+HyperpriorCharmVicModel` trains the unconditioned model (no beta pair, plain reductions) under `optim.g_scheduler`'s LinearWarmupScheduler
+(read_g_scheduler; `optim.g_optimizer` / `aux_optimizer` are read by read_rd_optimizers); over another model type it is refused.  It is the
+one stage that starts without a checkpoint: with neither --model_path nor --synthetic_weights the model is initialised from --seed by the
+reference's constructor rules (dc_vic_amd/train/init.py) around the pretrained VQGAN of `subnet.vq_model.ckpt_path`, which must exist.
+A stage 1-2 run starts from a stage 1-1 or a dual-conditioned checkpoint (--model_path) or synthetic weights: where the checkpoint's keys
+and the model's differ, rank 0 prints `[train] weights: N tensors loaded; missing ...; unexpected ...` by module, and the conditioning
+modules a stage 1-1 file lacks keep their constructor initialisation.
 """
 from __future__ import annotations
 
@@ -63,8 +70,9 @@ import torch
 sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dc_vic_amd import BaseConfig, build_comp_model  # noqa: E402
 from dc_vic_amd.parallel import launched_by_a_launcher, pin_rank_cpus, self_launch  # noqa: E402
-from dc_vic_amd.train.build import (build_discriminator, build_rd_trainer, build_trainer, choose_gan_trainer, choose_trainer, get_in,  # noqa: E402,F401
-                                    read_discriminator, read_gumbel_options)
+from dc_vic_amd.train.build import (RD_STAGE_1_1, build_discriminator, build_rd_trainer, build_trainer, choose_gan_trainer, choose_trainer,  # noqa: E402,F401
+                                    from_scratch_vqgan, get_in, read_discriminator, read_gumbel_options, weight_load_report)
+from dc_vic_amd.train.init import reference_init_  # noqa: E402
 from dc_vic_amd.train.data import HostFeed, TrainFeed, list_train_images, read_train_dataset  # noqa: E402
 from dc_vic_amd.train.losses import read_loss_section  # noqa: E402
 from dc_vic_amd.train.trainer import DEFAULT_LOSS  # noqa: E402
@@ -189,7 +197,9 @@ def main():
     if (a.data_workers is not None and a.data_workers < 0) or a.data_depth < 1:
         raise SystemExit(f"--data_workers {a.data_workers} / --data_depth {a.data_depth}: need workers >= 0 and depth >= 1")
     opt0 = BaseConfig.fromfile(a.config_path, {"is_train": True})
-    gan_kind = choose_trainer(opt0, a.gan)[0]                              # before any GPU work
+    gan_kind, trainer_name, _ = choose_trainer(opt0, a.gan)                # before any GPU work
+    from_scratch = trainer_name == RD_STAGE_1_1 and not a.model_path and not a.synthetic_weights
+    vqgan_path = from_scratch_vqgan(opt0) if from_scratch else None        # likewise: a start from the initialisation needs the VQGAN
     losses = read_loss_section(opt0)                                       # likewise: every `loss` entry is honoured or refused
     if gan_kind != "rd":
         read_gumbel_options(opt0)                                          # likewise
@@ -229,12 +239,20 @@ def main():
     ck = opt["subnet"]["vq_model"].get("ckpt_path")
     if ck and not os.path.exists(ck):
         opt["subnet"]["vq_model"]["ckpt_path"] = None
+    if from_scratch:
+        torch.manual_seed(a.seed)                   # identical initialisation on every rank
     model = build_comp_model(opt)
     if a.synthetic_weights:
         from dc_vic_amd.synth import load_synth_weights
         load_synth_weights(model, 1234)
+    elif from_scratch:
+        reference_init_(model, torch.Generator().manual_seed(a.seed))
+        if rank == 0:
+            print(f"[train] weights: initialised from seed {a.seed}; VQGAN from {vqgan_path}", flush=True)
     else:
-        model.load_learned_weight(ckpt_path=a.model_path)
+        line = weight_load_report(model.load_learned_weight(ckpt_path=a.model_path))
+        if line and rank == 0:
+            print("[train] " + line, flush=True)
     torch.manual_seed(a.seed)                       # identical D initialisation on every rank
     D, d_line = (None, None) if gan_kind == "rd" else build_discriminator(opt, device)             # the rate-distortion trainer has none
     w_perc = losses["weights"].get("perceptual", DEFAULT_LOSS["perceptual"])

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """samples/s of the stage-3 training step (BASELINE config 5: 256x256 crops, batch 8 per GPU, G + D step) -- a SEPARATE metric,
-never mixed into bench.py's headline.  python tools/train_bench.py [--gan {vanilla,oasis} | --stage 1_2 [--distortion {MSELoss,L1Loss,MSSSIMLoss}]] [--batch 8] [--steps 5] [--warmup 2]
+never mixed into bench.py's headline.  python tools/train_bench.py [--gan {vanilla,oasis} | --stage 1_2 [--distortion {MSELoss,L1Loss,MSSSIMLoss}] | --stage 1_1] [--batch 8] [--steps 5] [--warmup 2]
 [--disc_norm {none,batchnorm,actnorm}] [--disc unet]
 (--disc_norm: the discriminator's normalisation layers, csrc/bn_train.hip; --disc unet: the OASIS U-Net discriminator with --gan oasis; --gan oasis: the 257-class per-token discriminator of config/dc_vic_oasis.yaml and the OASIS cross-entropy loss; --stage 1_2: the
-rate-distortion step of train/rd_trainer.py with config/exp1_stage1_2.yaml's trainer and loss sections, no discriminator); under
+rate-distortion step of train/rd_trainer.py with config/exp1_stage1_2.yaml's trainer and loss sections, no discriminator; --stage 1_1: the
+unconditioned model's step with config/dc_vic_synthetic_stage1_1.yaml, from the synthetic weights the two models share); under
 torch.distributed.run it is data-parallel (weak scaling) and reports the aggregate."""
 import argparse
 import json
@@ -25,7 +26,8 @@ def main():
     p.add_argument("--gan", choices=("vanilla", "oasis"), default="vanilla")
     p.add_argument("--disc_norm", choices=("none", "batchnorm", "actnorm"), default="none", help="the discriminator's norm_type")
     p.add_argument("--disc", choices=("patchgan", "unet"), default="patchgan", help="unet: the OASIS U-Net discriminator (needs --gan oasis)")
-    p.add_argument("--stage", choices=("3", "1_2"), default="3", help="3: the G + D step (default); 1_2: the rate-distortion step")
+    p.add_argument("--stage", choices=("3", "1_2", "1_1"), default="3",
+                   help="3: the G + D step (default); 1_2: the rate-distortion step; 1_1: the unconditioned model's rate-distortion step")
     p.add_argument("--distortion", choices=("MSELoss", "L1Loss", "MSSSIMLoss"), default="MSELoss", help="--stage 1_2: distortion_loss.type")
     a = p.parse_args()
     rank, world, lr_ = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
@@ -39,9 +41,14 @@ def main():
         dist = dist_
     from dc_vic_amd import BaseConfig, build_comp_model
     from dc_vic_amd.synth import load_synth_weights
-    m = build_comp_model(BaseConfig.fromfile(os.path.join(ROOT, "config", "dc_vic_synthetic.yaml"), {"device": dev}))
+    cfg = BaseConfig.fromfile(os.path.join(ROOT, "config", "dc_vic_synthetic_stage1_1.yaml" if a.stage == "1_1" else "dc_vic_synthetic.yaml"), {"device": dev})
+    m = build_comp_model(cfg)
     load_synth_weights(m, 1234)
-    if a.stage == "1_2":
+    if a.stage == "1_1":
+        from dc_vic_amd.train.build import build_rd_stage_1_1_trainer
+        from dc_vic_amd.train.losses import read_loss_section
+        tr, what = build_rd_stage_1_1_trainer(cfg, read_loss_section(cfg), m, dist, rank, None)[0], "stage 1-1 rate-distortion step (unconditioned model)"
+    elif a.stage == "1_2":
         tr, what = rd_trainer(m, dist, rank, a.distortion), "stage 1-2 rate-distortion step" + (f" ({a.distortion})" if a.distortion != "MSELoss" else "")
     else:
         tr, what = gan_trainer(a, m, dev, dist, rank), "stage-3 G+D step"

@@ -1,5 +1,5 @@
 """ctypes binding of libdcvic_hip.so (include/dcvic.h, include/dcvic_loss.h, include/dcvic_rate.h, include/dcvic_train.h, include/dcvic_vq.h,
-include/dcvic_sample_loss.h, include/dcvic_gumbel.h, include/dcvic_msssim_loss.h, include/dcvic_data.h, include/dcvic_bn.h).  The library is REQUIRED: there is no
+include/dcvic_sample_loss.h, include/dcvic_gumbel.h, include/dcvic_msssim_loss.h, include/dcvic_data.h, include/dcvic_bn.h, include/dcvic_tokens.h).  The library is REQUIRED: there is no
 fallback path -- if it is missing or an entry point fails, the caller gets an exception."""
 from __future__ import annotations
 
@@ -143,6 +143,10 @@ BN_SIGNATURES = {
     "dcvic_bn_workspace_bytes": "q:iii", "dcvic_bn_stats_f32": "i:pqpppqiiip", "dcvic_bn_train_fwd_f32": "i:pqpqppppddppipqiiip",
     "dcvic_bn_train_bwd_f32": "i:pqpqpqppppqppiipqiiip", "dcvic_actnorm_fwd_f32": "i:pqpqppiiiip", "dcvic_actnorm_bwd_f32": "i:pqpqpqpppqppiipqiiip",
 }
+# include/dcvic_tokens.h: a stored selection set's ingest, uint8 crops to fp32 NCHW and VQ tokens to idx / zq / feat (csrc/tokens.hip)
+TOKEN_SIGNATURES = {
+    "dcvic_u8_hwc_to_f32_nchw": "i:piiippp", "dcvic_vq_token_feat_f32": "i:pipiiiiipppp",
+}
 VQ_NONE, VQ_SHARD, VQ_PACKED2, VQ_PACKED1, VQ_LDS4, VQ_LDS8 = range(6)
 
 _lib = None
@@ -164,7 +168,7 @@ def lib() -> C.CDLL:
     L = C.CDLL(LIB_PATH)
     for name, sig in (*SIGNATURES.items(), *LOSS_SIGNATURES.items(), *RATE_SIGNATURES.items(), *TRAIN_SIGNATURES.items(), *VQ_SIGNATURES.items(),
                       *SAMPLE_LOSS_SIGNATURES.items(), *GUMBEL_SIGNATURES.items(), *MSSSIM_LOSS_SIGNATURES.items(),
-                      *DATA_SIGNATURES.items(), *BN_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
+                      *DATA_SIGNATURES.items(), *BN_SIGNATURES.items(), *TOKEN_SIGNATURES.items()):     # the package's only restype / argtypes assignments; other symbols stay untyped
         fn = getattr(L, name)                # AttributeError names a symbol the library lacks
         ret, params = sig.split(":")
         fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[c] for c in params]

@@ -435,10 +435,16 @@ class HyperpriorVicModel(BaseModel):
         """Returns (gt_vq_latent, gt_vq_indices[, feat = cat[latent, onehot]])."""
         if vq_indices is not None:
             # pre-computed tokens (scripts/build_openimage_val_dataset.py -> binary_rate_search / beta_selection callers)
-            idx = vq_indices.to(real_images.device).long()
-            zq = self.vq_indices_to_latent(idx)
+            # uint8 / int64 tokens on the device go to the kernel as they are; anything else becomes int64 on the device first.  One
+            # launch writes idx, zq and feat with the bits of vq_indices_to_latent and _index_feat (csrc/tokens.hip)
+            tok = vq_indices
+            if not (tok.device == real_images.device and tok.dtype in (torch.uint8, torch.int64)):
+                tok = tok.to(real_images.device).long()
+            given = tok.dtype == torch.int64       # .long() of an int64 tensor is that tensor: return it, as before
+            idx, zq, feat = ops.vq_token_feat(tok.contiguous(), self.vq_model.quantize.embedding.weight, want_idx=not given, want_feat=want_feat)
+            idx = tok if given else idx
             if want_feat:
-                return zq, idx, self._index_feat(zq, idx)
+                return zq, idx, feat
             return zq, idx
         N, _, H, W = real_images.shape
         _z = self._vq_encode_split(real_images) if max(H, W) > SPLIT_DECODE_RESOLUTION else self.vq_model.encode(real_images)
@@ -453,7 +459,8 @@ class HyperpriorVicModel(BaseModel):
 
     def _index_feat(self, latent: Tensor, indices: Tensor) -> Tensor:
         """cat[latent, one_hot(indices)] from the indices GIVEN (hyperprior_vic_model.py:268-271), not from a search of the gathered
-        latent: the search returns the first of two equal codebook rows, whatever index the caller holds.  Off the hot path."""
+        latent: the search returns the first of two equal codebook rows, whatever index the caller holds.  The torch form, for callers
+        that hold a latent already; vq_encode with tokens gets the same bits from dcvic_vq_token_feat_f32."""
         n_e = self.vq_model.quantize.embedding.weight.shape[0]
         onehot = torch.nn.functional.one_hot(indices.long(), n_e).permute(0, 3, 1, 2).to(latent.dtype)
         return torch.cat([latent, onehot], dim=1).contiguous()

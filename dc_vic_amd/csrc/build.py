@@ -14,11 +14,11 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT = os.path.join(os.path.dirname(HERE), "libdcvic_hip.so")
-SOURCES = ["conv.hip", "conv3x3.hip", "wino.hip", "wino44.hip", "wino44_ups.hip", "conv_bf16.hip", "thin.hip", "conv_async.hip", "conv_async16.hip", "conv1x1.hip", "gemm.hip", "attn.hip", "norm.hip", "ew.hip", "swin.hip", "vq.hip", "rate.hip", "rate_train.hip", "train.hip", "chan_ce.hip", "sample_loss.hip", "bn_train.hip", "gumbel.hip", "metrics.hip", "fid.hip", "ssim.hip", "msssim_loss.hip", "data.hip", "error.cpp", "host_entropy.cpp"]
+SOURCES = ["conv.hip", "conv3x3.hip", "wino.hip", "wino44.hip", "wino44_ups.hip", "conv_bf16.hip", "thin.hip", "conv_async.hip", "conv_async16.hip", "conv1x1.hip", "gemm.hip", "attn.hip", "norm.hip", "ew.hip", "swin.hip", "vq.hip", "rate.hip", "rate_train.hip", "train.hip", "chan_ce.hip", "sample_loss.hip", "bn_train.hip", "gumbel.hip", "metrics.hip", "fid.hip", "ssim.hip", "msssim_loss.hip", "data.hip", "tokens.hip", "error.cpp", "host_entropy.cpp"]
 HEADERS = [os.path.join(HERE, "common.h"), os.path.join(HERE, "conv_common.h"), os.path.join(HERE, "wino_stream.h"), os.path.join(HERE, "chan_ce_core.h"), os.path.join(HERE, "vq_lut.h"), os.path.join(HERE, "ssim_core.h"), os.path.join(ROOT, "include", "dcvic.h"), os.path.join(ROOT, "include", "dcvic_loss.h"),
            os.path.join(ROOT, "include", "dcvic_rate.h"), os.path.join(ROOT, "include", "dcvic_train.h"), os.path.join(ROOT, "include", "dcvic_vq.h"),
            os.path.join(ROOT, "include", "dcvic_sample_loss.h"), os.path.join(ROOT, "include", "dcvic_gumbel.h"), os.path.join(ROOT, "include", "dcvic_msssim_loss.h"),
-           os.path.join(ROOT, "include", "dcvic_data.h"), os.path.join(ROOT, "include", "dcvic_bn.h")]
+           os.path.join(ROOT, "include", "dcvic_data.h"), os.path.join(ROOT, "include", "dcvic_bn.h"), os.path.join(ROOT, "include", "dcvic_tokens.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-value", "-Wno-unused-result",
          f"-I{os.path.join(ROOT, 'include')}", f"-I{HERE}"]
 

@@ -683,6 +683,48 @@ def argmax_lut(logits: Tensor, codebook: Tensor, pq_w: Tensor, pq_b: Optional[Te
     return idx, lat
 
 
+def _on_current_device(t: Tensor, name: str) -> None:
+    if not t.is_cuda or t.device.index != torch.cuda.current_device():
+        raise ValueError(f"{name} lives on {t.device} but the current HIP device is cuda:{torch.cuda.current_device() if torch.cuda.is_available() else '-'}")
+
+
+def vq_token_feat(tokens: Tensor, codebook: Tensor, want_idx: bool = True, want_zq: bool = True, want_feat: bool = False):
+    """Stored VQ tokens [N, h, w] (uint8 or int64, on the device) -> (idx int64 [N, h, w], zq [N, D, h, w], feat [N, D + n_e, h, w]) in
+    one launch (csrc/tokens.hip, include/dcvic_tokens.h); an output not wanted is None.  zq carries the bits of
+    embedding(idx).permute(0, 3, 1, 2), feat those of cat[zq, one_hot(idx)]."""
+    if tokens.dim() != 3 or tokens.dtype not in (torch.uint8, torch.int64) or not tokens.is_contiguous():
+        raise ValueError(f"vq_token_feat: tokens must be contiguous uint8 or int64 [N, h, w], got {tokens.dtype} {tuple(tokens.shape)}")
+    if codebook.dim() != 2 or codebook.dtype != torch.float32 or not codebook.is_contiguous() or codebook.device != tokens.device:
+        raise ValueError(f"vq_token_feat: codebook must be contiguous fp32 [n_e, D] on {tokens.device}, got {codebook.dtype} "
+                         f"{tuple(codebook.shape)} {codebook.device}")
+    _on_current_device(tokens, "vq_token_feat: tokens")
+    N, h, w = tokens.shape
+    n_e, D = codebook.shape
+    idx = torch.empty((N, h, w), dtype=torch.int64, device=tokens.device) if want_idx else None
+    zq = torch.empty((N, D, h, w), dtype=torch.float32, device=tokens.device) if want_zq else None
+    feat = torch.empty((N, D + n_e, h, w), dtype=torch.float32, device=tokens.device) if want_feat else None
+    check(lib().dcvic_vq_token_feat_f32(_p(tokens), tokens.element_size(), _p(codebook), N, h, w, D, n_e, _p(idx), _p(zq), _p(feat), _stream()),
+          "vq_token_feat")
+    return idx, zq, feat
+
+
+def u8_hwc_to_f32_nchw(src: Tensor, table: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """uint8 [N, H, W, 3] on the device (any dense view, e.g. a slice of a resident array at any byte offset) -> fp32 [N, 3, H, W],
+    out[n, c, y, x] = table[src[n, y, x, c]] (csrc/tokens.hip, include/dcvic_tokens.h)."""
+    if src.dim() != 4 or src.shape[3] != 3 or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError(f"u8_hwc_to_f32_nchw: src must be contiguous uint8 [N, H, W, 3], got {src.dtype} {tuple(src.shape)}")
+    if table.dtype != torch.float32 or table.numel() != 256 or not table.is_contiguous() or table.device != src.device:
+        raise ValueError(f"u8_hwc_to_f32_nchw: table must be 256 fp32 on {src.device}, got {table.dtype} {tuple(table.shape)} {table.device}")
+    _on_current_device(src, "u8_hwc_to_f32_nchw: src")
+    N, H, W, _ = src.shape
+    if out is None:
+        out = torch.empty((N, 3, H, W), dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (N, 3, H, W) or not out.is_contiguous() or out.device != src.device:
+        raise ValueError(f"u8_hwc_to_f32_nchw: out {out.dtype} {tuple(out.shape)} {out.device}, expected ({N}, 3, {H}, {W}) fp32 on {src.device}")
+    check(lib().dcvic_u8_hwc_to_f32_nchw(_p(src), N, H, W, _p(table), _p(out), _stream()), "u8_hwc_to_f32_nchw")
+    return out
+
+
 def gumbel_lut(logits: Tensor, noise: Tensor, codebook: Tensor, pq_w: Tensor, pq_b: Optional[Tensor], tau: float = 1.0):
     """The hard Gumbel-softmax sample of training mode (F.gumbel_softmax(logits, tau, hard=True, dim=1) for the draw `noise` ~ Exp(1),
     times the codebook, through post_quant_conv): idx = first argmax of logits - log(noise), lat as argmax_lut forms it."""

@@ -36,10 +36,11 @@ import torch
 
 sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.append(os.path.dirname(os.path.abspath(__file__)))
-from binary_rate_search import batches, load_dataset  # noqa: E402
+from binary_rate_search import batches  # noqa: E402
 from calc_metrics import FID_MIN_IMAGES, average_psnr, fid_metric, fid_statistics  # noqa: E402
 from dc_vic_amd import BaseConfig, build_comp_model, ops  # noqa: E402
 from dc_vic_amd.io_pipeline import AsyncWriter, encode_png_u8  # noqa: E402
+from dc_vic_amd.selection_set import SelectionSet  # noqa: E402
 
 SEARCH_ERROR_THRESHOLD = 0.001
 
@@ -66,12 +67,13 @@ def arg_parse() -> dict:
 
 @torch.no_grad()
 def save_reconstructions(model, items, names, bs, save_dir, beta_vq, beta_rate) -> float:
-    """beta_selection.py:119-155: run_model on every batch, write <name>.png + the per-image rate table."""
+    """beta_selection.py:119-155: run_model on every batch, write <name>.png + the per-image rate table.  `items`: the list of
+    load_dataset, or a SelectionSet (the same batches, from device memory where the folder allows)."""
     rows = []
     writer = AsyncWriter()
     k = 0
     try:
-        for x, idx in batches(items, bs):
+        for x, idx in (items.batches(bs) if isinstance(items, SelectionSet) else batches(items, bs)):
             N, _, H, W = x.shape
             out = model.run_model(real_images=x, vq_indices=idx, beta_vq=beta_vq, beta_rate=beta_rate, is_train=False)
             bits = out["bits_per_image"].double().cpu().numpy()
@@ -118,10 +120,10 @@ def main() -> None:
         inception = FIDInception.from_file(a["inception_path"])
     os.makedirs(a["save_dir"], exist_ok=True)
     assert os.path.exists(a["dataset_root"]), f'dataset_root "{a["dataset_root"]}" does not exist.'
-    items = load_dataset(a["dataset_root"])
-    names = [os.path.basename(p) for p in sorted(glob(os.path.join(a["dataset_root"], "*.png")))]
-    assert items, f'dataset_root "{a["dataset_root"]}" holds no png'
     model = build_comp_model(opt)
+    items = SelectionSet(a["dataset_root"], model.device, opt["subnet"]["vq_model"]["n_embed"])
+    names = items.names
+    assert len(items), f'dataset_root "{a["dataset_root"]}" holds no png'
     if a["synthetic_weights"]:
         from dc_vic_amd.synth import load_synth_weights
         load_synth_weights(model, 1234)

@@ -6,6 +6,8 @@ path, same flags, loop and csv output as the reference's scripts/b
 The dataset is a directory of <name>.png (+ optional <name>.npy pre-computed VQ tokens, as written by
 build_openimage_val_dataset.py; without the .npy the tokens are computed by the VQGAN encoder on the fly).
 Each probe runs vq_encode -> comp_encode -> estimate_entropy -> get_rate_summary_dict on the GPU.
+The folder is read once into a dc_vic_amd.selection_set.SelectionSet: where every crop has one shape (and all or none have tokens) the
+images and tokens stay on the device as uint8 for all probes, and a probe's per-batch bpp values come down in one copy.
 `--synthetic_weights` replaces --model_path by the deterministic synthetic weights.
 """
 from __future__ import annotations
@@ -22,6 +24,7 @@ import torch
 
 sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dc_vic_amd import BaseConfig, build_comp_model  # noqa: E402
+from dc_vic_amd.selection_set import SelectionSet, host_batches, host_item  # noqa: E402
 
 MEMO_DICT = {}
 MAX_RUN_CNT = 10
@@ -44,41 +47,38 @@ def arg_parse() -> dict:
 
 
 def load_dataset(root: str):
+    """The folder as a host list of (x fp32 [3, H, W], int64 tokens or None); tokens are taken as they are (SelectionSet validates them)."""
     from PIL import Image
     items = []
     for path in sorted(glob(os.path.join(root, "*.png"))):
         img = np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
-        x = (torch.from_numpy(img.copy()).permute(2, 0, 1).float().div(255.0) - 0.5) / 0.5
         npy = path.replace(".png", ".npy")
-        idx = torch.from_numpy(np.load(npy).astype(np.int32)).long() if os.path.exists(npy) else None
-        items.append((x, idx))
+        items.append(host_item(img, np.load(npy) if os.path.exists(npy) else None))
     return items
 
 
 def batches(items, bs):
     """consecutive items of equal shape share a batch (the reference's DataLoader needs equal shapes too)"""
-    i = 0
-    while i < len(items):
-        j = i + 1
-        while j < len(items) and j - i < bs and items[j][0].shape == items[i][0].shape and (items[j][1] is None) == (items[i][1] is None):
-            j += 1
-        x = torch.stack([it[0] for it in items[i:j]])
-        idx = torch.stack([it[1] for it in items[i:j]]) if items[i][1] is not None else None
-        yield x, idx
-        i = j
+    return host_batches(items, bs)
 
 
 @torch.no_grad()
 def run_one_search(model, items, bs, beta_rate: float, beta_vq: float) -> float:
+    """`items`: the list of load_dataset, or a SelectionSet.  For a set the per-batch bpp values (0-dim fp64 tensors) stay on the device
+    and come down once per probe; their fp64 mean is np.mean of the same values, as for the list."""
+    in_set = isinstance(items, SelectionSet)
     bpp_list = []
-    for x, idx in batches(items, bs):
+    for x, idx in (items.batches(bs) if in_set else batches(items, bs)):
         N, _, H, W = x.shape
         pi = model.data_preprocess(vq_indices=idx, real_images=x, beta_rate=beta_rate, beta_vq=beta_vq, is_train=False)
-        gt_vq_latent, gt_vq_indices = model.vq_encode(pi["real_images"], pi["vq_indices"])
+        gt_vq_latent, gt_vq_indices, feat = model.vq_encode(pi["real_images"], pi["vq_indices"], want_feat=True)      # feat from the kernel, as run_model
         y = model.comp_encode(real_images=pi["real_images"], gt_vq_latent=gt_vq_latent, gt_vq_indices=gt_vq_indices,
-                              enc_kwargs=dict(beta_1=beta_rate, beta_2=beta_vq))
+                              enc_kwargs=dict(beta_1=beta_rate, beta_2=beta_vq), feat=feat)
         entropy_dict = model.estimate_entropy(y, is_train=False)
-        bpp_list.append(float(model.get_rate_summary_dict(entropy_dict, num_pixel=N * H * W)["bpp"]))
+        bpp = model.get_rate_summary_dict(entropy_dict, num_pixel=N * H * W)["bpp"]
+        bpp_list.append(bpp if in_set else float(bpp))
+    if in_set:
+        bpp_list = torch.stack(bpp_list).cpu().numpy()
     return float(np.mean(bpp_list))
 
 
@@ -124,8 +124,8 @@ def main() -> None:
         load_synth_weights(model, 1234)
     else:
         model.load_learned_weight(ckpt_path=args["model_path"])
-    items = load_dataset(args["dataset_root"])
-    assert items, f'dataset_root "{args["dataset_root"]}" holds no png'
+    items = SelectionSet(args["dataset_root"], model.device, opt["subnet"]["vq_model"]["n_embed"])
+    assert len(items), f'dataset_root "{args["dataset_root"]}" holds no png'
     for beta_vq, target_rate in product(args["beta_vq"], args["target_rate"]):
         df = run(args, model, items, target_rate, beta_vq)
         df.to_csv(os.path.join(args["save_dir"], f"result_beta_vq_{beta_vq:.2f}_target_rate_{target_rate:.3f}.csv"))
